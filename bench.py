@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the batched ALGAMES Newton / augmented-Lagrangian hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config C2|C3|C4|C5]
+    python bench.py --gpus N --steps K --warmup W [--config C2|C3|C4|C5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -20,6 +20,11 @@ performed a linear solve, summed over games and ranks) -- BASELINE.json's "Newto
 games-to-convergence/s is reported next to it.  Weak scaling: the scenario batch is sharded by contiguous
 global scenario ids, one rank per GPU, no data-path collective (games are independent); the only collectives
 are the timing barrier / max and the final count reduction.
+
+A plain run sets up, warms up, times the K steps and prints the result line; the roofline object then holds the accounting
+of this run's own timings (and the newest committed counter profile of the workload, labelled as such).  --full adds what
+takes runs of its own: the in-run rocprofv3 counter passes and the CPU baseline (the oracle on the same workload).
+--dump-outputs DIR writes what the last timed step computed as float64 .npy files (see dump_outputs()).
 
 Prints ONE JSON line on rank 0.
 """
@@ -251,6 +256,40 @@ def inrun_pmc(argv_tail, kernel, iters_per_launch, own_bytes, timeout_s=150):
     return res
 
 
+DUMP_BYTES = 56_000_000    # --dump-outputs: data bytes of all files together (the limit is 64 MB; the rest is headroom for the headers)
+DUMP_SEED = 1234           # fixed sample of games when a batch's outputs exceed DUMP_BYTES
+
+
+def dump_outputs(outdir, b, ids, st, mpc=None):
+    """--dump-outputs: what a caller of the timed path receives after the last timed step, one float64 .npy per array:
+      pdtraj            (G, traj_len) the primal-dual trajectory (alg_get_traj)
+      con_lambda/_mu    (G, con_len)  constraint multipliers and penalties (alg_get_con_duals)
+      stats_<field>     (G,)          the per-game statistics of alg_get_stats (status, iteration counts, ...)
+      last_<field>      (G,)          the final record of every game (residual, violations, step; not its wall time)
+      mpc_newton_iters, mpc_converged (G,)  receding-horizon mode: the per-game totals of the loop
+      game_ids          (G,)          global scenario ids of the rows
+    When the arrays of the whole batch exceed DUMP_BYTES a fixed, seeded sample of games is written (same rows every run).
+    Rank 0 writes its own shard."""
+    import numpy as np
+    z = b.get_traj()
+    lam, mu = b.get_con_duals()
+    cols = {"pdtraj": z, "con_lambda": lam, "con_mu": mu, "game_ids": np.asarray(ids)}
+    for f in ("status", "outer_iters", "newton_iters", "records", "converged", "ls_failures", "refinements"):
+        cols["stats_" + f] = st[f]
+    for f in ("outer", "ls_j", "alpha", "res", "delta", "dyn_vio", "con_vio", "sta_vio", "opt_vio"):
+        cols["last_" + f] = st["last"][f]
+    if mpc is not None:
+        cols["mpc_newton_iters"], cols["mpc_converged"] = mpc
+    G = z.shape[0]
+    per_game = 8 * sum(int(np.prod(a.shape[1:])) for a in cols.values())
+    k = min(G, DUMP_BYTES // per_game)
+    rows = np.arange(G) if k == G else np.sort(np.random.default_rng(DUMP_SEED).choice(G, k, replace=False))
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in cols.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(np.asarray(a)[rows], dtype=np.float64))
+    return {"dir": outdir, "games": int(k), "games_in_batch": int(G), "files": len(cols), "bytes": int(k * per_game)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -279,8 +318,13 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed with the nccl (= RCCL) backend even for one rank, so that communicator creation, the "
                          "barrier and the two all-reduces of the counter reduction run on the device (tests/test_gpu_bench_ranks.py)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the in-run rocprofv3 counter passes (the children of a run use this)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the in-run rocprofv3 counter passes and the CPU baseline (off by default)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true",
+                    help="skip the in-run rocprofv3 counter passes of --full and the committed counter profile (the children of a run use this)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step computed to DIR/<name>.npy (float64, at most 64 MB; rank 0's shard)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
@@ -391,6 +435,9 @@ def main():
         iters_rank = int(st["newton_iters"].sum())
         conv_rank = int(st["converged"].sum())
         per_game = st["newton_iters"]
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, b, ids, st, (it_, cv_) if args.mpc_steps else None)
     # one launch lasts as long as its slowest game: mean / max of the per-game iteration counts (1.0 = homogeneous batch)
     balance = float(per_game.mean() / max(1, per_game.max()))
     bad_rank = int((st["status"] != 0).sum())
@@ -426,7 +473,7 @@ def main():
             roof["outer_passes_per_launch"] = {"record": n_out, "dual_update": n_dual}
             roof["bytes_per_game_iter_outer_passes"] = (n_out * rec_b + n_dual * dual_b) / max(1, iters_rank)
         pmc = None
-        if world == 1 and not args.no_pmc:
+        if world == 1 and args.full and not args.no_pmc:
             tail = ["--config", args.config, "--games-per-gpu", str(G), "--waves-per-game", str(args.waves_per_game),     # (a 1-GPU child: weak)
                     "--refine-steps", str(refine_steps), "--refine-tol", repr(refine_tol)]
             if args.mpc_steps:
@@ -448,7 +495,8 @@ def main():
                 for k in ("valu_issue_frac", "mfma_frac", "wave_issue_frac", "traffic_over_model"):
                     if k in pj:
                         roof[k] = pj[k]
-                roof["pmc_source"] = "committed: " + os.path.relpath(pf, ROOT) + " (the in-run rocprofv3 passes were not available; not re-measured in this run)"
+                roof["pmc_source"] = "committed: " + os.path.relpath(pf, ROOT) + (" (the in-run rocprofv3 passes were not available; not re-measured in this run)" if args.full
+                                                                                 else " (not re-measured: a plain run makes no counter passes, --full does)")
         out = {
             "metric": "newton_iters_per_sec", "value": value, "unit": "game-Newton-iterations/s",
             "n_gpus": world, "steps": K, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / K,
@@ -471,7 +519,9 @@ def main():
             "games_converged": conv_all, "games_failed": bad_all,
             "roofline": roof,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if dumped is not None:
+            out["dump_outputs"] = dumped
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(alg, family, G, args.mpc_steps, cfg_kw)
         print(json.dumps(out))
     if use_dist:

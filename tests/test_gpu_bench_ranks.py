@@ -7,17 +7,18 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(*args, shared=False):
+def _bench(*args, shared=False, plain=False):
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     if shared:
         env["ALGAMES_BENCH_SHARED_DEVICE"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-pmc", *args],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1"] + ([] if plain else ["--no-cpu-baseline", "--no-pmc"]) + list(args),
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -98,3 +99,31 @@ def test_a_failing_rank_fails_the_job():
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode != 0
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]                # no result line from a job that lost a rank
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_last_step_and_repeats_it_exactly(tmp_path):
+    """A run without --full measures no CPU baseline and makes no counter passes; --dump-outputs writes what the last timed step
+    computed (float64), all 512 games of the batch, and a second run with the same arguments writes the very same arrays."""
+    a = _bench("--games-per-gpu", "512", "--dump-outputs", str(tmp_path / "a"), plain=True)
+    b = _bench("--games-per-gpu", "512", "--dump-outputs", str(tmp_path / "b"), plain=True)
+    for d in (a, b):
+        assert "cpu_baseline" not in d and not str(d["roofline"].get("pmc_source", "")).startswith("in-run")
+        assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["dump_outputs"]["games"] == 512
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "pdtraj.npy" in names and "con_lambda.npy" in names
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64_000_000
+    for f in names:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype == np.float64 and x.shape[0] == 512 and np.array_equal(x, y), f
+    assert np.array_equal(np.load(tmp_path / "a" / "game_ids.npy"), np.arange(512))
+    assert np.load(tmp_path / "a" / "stats_newton_iters.npy").sum() == a["config"]["newton_iters_per_solve_total"]
+    assert np.load(tmp_path / "a" / "stats_converged.npy").sum() == a["games_converged"] == 512
+    assert np.isfinite(np.load(tmp_path / "a" / "pdtraj.npy")).all()
+
+
+@pytest.mark.gpu
+def test_full_run_adds_the_cpu_baseline():
+    """--full keeps the measurements that take runs of their own; the CPU baseline is checked here (the counter passes are skipped)."""
+    d = _bench("--games-per-gpu", "256", "--full", "--no-pmc", plain=True)
+    assert d["games_converged"] == 256 and d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["single_core_value"] > 0
