@@ -14,6 +14,11 @@ ALG_MODEL_BICYCLE = 2
 ALG_MODEL_QUADROTOR = 3
 ALG_TRAJ_PD, ALG_TRAJ_TRIAL, ALG_TRAJ_DELTA = 0, 1, 2
 ALG_STATUS_OK, ALG_STATUS_SINGULAR, ALG_STATUS_NAN = 0, 1, 2
+ALG_ERR_ARG, ALG_ERR_DEVICE, ALG_ERR_STATE = -1, -2, -3
+# kinds of per-game scenario data (alg_set_scenario_data)
+(ALG_SCEN_COLLISION_RADIUS, ALG_SCEN_COLLISION_COST, ALG_SCEN_CONTROL_BOUND, ALG_SCEN_STATE_BOUND,
+ ALG_SCEN_WALL, ALG_SCEN_CIRCLE, ALG_SCEN_WALL3D, ALG_SCEN_CYLINDER) = range(8)
+SCEN_KINDS = ("collision_radius", "collision_cost", "control_bound", "state_bound", "wall", "circle", "wall3d", "cylinder")
 
 
 class alg_desc(C.Structure):
@@ -136,7 +141,13 @@ SIGNATURES = {
     "mpc_advance": (C.c_int, [_P]),
     "mpc_totals": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32]),
     "mpc_solve": (C.c_int, [_P, C.c_int32, C.c_int64, _D]),
+    "scenario_data_len": (C.c_int, [_P, C.c_int32, _I]),
+    "set_scenario_data": (C.c_int, [_P, C.c_int32, _D]),
+    "get_scenario_data": (C.c_int, [_P, C.c_int32, _D]),
 }
+# Entry points a backend may lack (the CPU oracle has no per-game scenario data): bound when present; calling one that is absent
+# raises AlgamesError naming the backend.
+OPTIONAL = frozenset({"scenario_data_len", "set_scenario_data", "get_scenario_data"})
 
 
 class AlgamesError(RuntimeError):
@@ -171,16 +182,26 @@ class CLib:
         self.path, self.prefix = path, prefix
         self.dll = C.CDLL(path)
         self.missing = []
+        self.absent = []        # optional entry points this backend does not export
         for name, (res, args) in SIGNATURES.items():
             try:
                 fn = getattr(self.dll, prefix + name)
             except AttributeError:
-                self.missing.append(prefix + name)
+                if name in OPTIONAL:
+                    self.absent.append(name)
+                    setattr(self, name, self._absent_fn(name))
+                else:
+                    self.missing.append(prefix + name)
                 continue
             fn.restype, fn.argtypes = res, args
             setattr(self, name, fn)
         if self.missing:
             raise AlgamesError(f"{path}: missing ABI symbols {self.missing}")
+
+    def _absent_fn(self, name):
+        def absent(*args):
+            raise AlgamesError(f"{self.path}: this backend has no {self.prefix}{name} (per-game scenario data is not supported by it)")
+        return absent
 
     def check(self, rc):
         if rc != ALG_OK:
@@ -390,6 +411,45 @@ class Batch:
         ax = np.ascontiguousarray(axis, dtype=np.int32)
         self.lib.check(self.lib.add_cylinder_constraint_player(self.h, int(player), len(p), _dptr(p), ax.ctypes.data_as(_I), _dptr(_f64(l, (len(p),))), _dptr(_f64(r, (len(p),)))))
         self._refresh_con_len()
+
+    # ---- per-game scenario data ----------------------------------------------------------------
+    @staticmethod
+    def _kind(kind):
+        if isinstance(kind, str):
+            if kind not in SCEN_KINDS:
+                raise ValueError(f"unknown scenario kind {kind!r}; one of {SCEN_KINDS}")
+            return SCEN_KINDS.index(kind)
+        k = int(kind)
+        if not 0 <= k < len(SCEN_KINDS):
+            raise ValueError(f"unknown scenario kind {kind!r}")
+        return k
+
+    def scenario_data_len(self, kind):
+        """Doubles per game of `kind` (an ALG_SCEN_* value or its name in SCEN_KINDS); 0 if that kind was not added."""
+        v = C.c_int32()
+        self.lib.check(self.lib.scenario_data_len(self.h, self._kind(kind), C.byref(v)))
+        return v.value
+
+    def set_scenario_data(self, kind, data):
+        """Per-game values of one kind (B x scenario_data_len(kind)); None = back to the handle's shared values.  See
+        alg_set_scenario_data for what is checked and when the multipliers are re-created."""
+        k = self._kind(kind)
+        if data is None:
+            self.lib.check(self.lib.set_scenario_data(self.h, k, None))
+            return
+        L = self.scenario_data_len(k)
+        a = np.ascontiguousarray(np.asarray(data, dtype=np.float64))
+        if a.shape != (self.B, L):
+            raise ValueError(f"scenario data of kind {SCEN_KINDS[k]!r}: expected shape {(self.B, L)}, got {a.shape}")
+        self.lib.check(self.lib.set_scenario_data(self.h, k, _dptr(a)))
+        self._refresh_con_len()
+
+    def get_scenario_data(self, kind):
+        k = self._kind(kind)
+        L = self.scenario_data_len(k)
+        out = np.empty((self.B, L))
+        self.lib.check(self.lib.get_scenario_data(self.h, k, _dptr(out)))
+        return out
 
     # ---- data movement -----------------------------------------------------------------------
     def set_traj(self, z, which=ALG_TRAJ_PD):

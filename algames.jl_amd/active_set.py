@@ -212,12 +212,19 @@ def active_horizontal_mask(ascore, game_con):
                         ascore.hmask += horizontal_idx(ascore, s)
 
 
+def game_con_of(prob, game):
+    """The GameConstraintValues of game `game` of a problem: its own entry when the problem was built from one per game
+    (GameProblem(..., game_con=[...]): the games may differ in radii), else the problem's shared one."""
+    cons = getattr(prob, "game_cons", None)
+    return prob.game_con if cons is None else cons[game]
+
+
 def _game_state(prob, game):
     X = prob.pdtraj.states[game]
     lam, _ = prob.batch.get_con_duals()
     ps = prob.probsize
     K = ps.N - 1
-    cvs = collision_convals(prob.game_con)
+    cvs = collision_convals(game_con_of(prob, game))
     for (i, j), cv in cvs.items():                  # ABI layout: pair q = (i, j) in add_collision_avoidance! order, knots 2..N
         q = (i - 1) * (ps.p - 1) + ((j - 1) if j < i else (j - 2))
         cv.λ[:] = lam[game, q * K:(q + 1) * K]
@@ -231,8 +238,9 @@ def residual(ascore, prob, game=0):
     ascore.res[:] = 0.0
     ascore.res[:ps.S] = host.residual(prob)[game]
     X = _game_state(prob, game)
-    evaluate(prob.game_con, X)
-    for (i, j), cv in collision_convals(prob.game_con).items():
+    gc = game_con_of(prob, game)
+    evaluate(gc, X)
+    for (i, j), cv in collision_convals(gc).items():
         if i < j:
             for l, k in enumerate(cv.inds):
                 s = CStamp("v", "col", i, j, k)
@@ -252,8 +260,9 @@ def residual_jacobian(ascore, prob, game=0, constraint_rows=False):
     ascore.jac[:ps.S, :ps.S] = host.residual_jacobian(prob, 0.0, games=(game, 1))[0]      # this game only, and give the device copy back
     prob.batch.release_scratch()
     X = _game_state(prob, game)
-    evaluate(prob.game_con, X)
-    for (i, j), cv in collision_convals(prob.game_con).items():
+    gc = game_con_of(prob, game)
+    evaluate(gc, X)
+    for (i, j), cv in collision_convals(gc).items():
         for l, k in enumerate(cv.inds):
             vs = ("opt", i, "x", 1, k)
             cs = CStamp("h", "col", i, j, k)
@@ -292,9 +301,10 @@ def nullspace(A, atol=1e-20):
 def update_nullspace(ascore, prob, game=0, atol=1e-20, constraint_rows=False):
     """update_nullspace!(ascore, prob, pdtraj), active_set_methods.jl:173-184."""
     X = _game_state(prob, game)
-    update_active_set(prob.game_con, X, tol=getattr(prob.opts, "active_set_tolerance", 0.0))
-    active_vertical_mask(ascore, prob.game_con)
-    active_horizontal_mask(ascore, prob.game_con)
+    gc = game_con_of(prob, game)
+    update_active_set(gc, X, tol=getattr(prob.opts, "active_set_tolerance", 0.0))
+    active_vertical_mask(ascore, gc)
+    active_horizontal_mask(ascore, gc)
     residual_jacobian(ascore, prob, game, constraint_rows=constraint_rows)
     djac = ascore.jac[np.ix_(np.asarray(ascore.vmask) - 1, np.asarray(ascore.hmask) - 1)]
     ascore.null.reset()

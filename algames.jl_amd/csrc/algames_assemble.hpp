@@ -100,6 +100,20 @@ __device__ __forceinline__ T sel_player(const ALG_AS4 T* tab, int i, F&& f) {
     for (int q = 1; q < NP; q++) v = (i == q) ? tab[f(q)] : v;
     return v;
 }
+// The same selection for a per-player scenario number: the EXT instantiations take it from the game's scenario block (uniform-address
+// loads at constant offsets), the base ones from the kernel-argument table as before.
+template <class C, int NP, class F>
+__device__ __forceinline__ double scen_player(CPR pr, const Game& G, const ALG_AS4 double* shared, int off, int i, F&& f) {
+    if constexpr (C::EXT) {
+        const double* tab = G.scen(pr) + off;
+        double v = tab[f(0)];
+#pragma unroll
+        for (int q = 1; q < NP; q++) v = (i == q) ? tab[f(q)] : v;
+        return v;
+    } else {
+        return sel_player<NP>(shared, i, f);
+    }
+}
 // The pair / own-position terms of ONE item of phase A -- (knot k + 1, player i): collision cost and collision avoidance of the ordered pairs
 // (i, j), the extended set's wall / circle terms -- shared by the pass over all steps (assemble_phase_a) and the per-chunk form of the fused pass
 // (round 6).  xp(idx): entry idx of x_{k+1} of the (trial) iterate; lmu(jj, ci, lam, mu): multiplier and penalty of constraint row ci (pair jj);
@@ -133,8 +147,8 @@ __device__ __forceinline__ void phase_a_pos_item(CPR pr, const Game& G, int N, i
                 if (pr.has_colavoid) lmu(jj, con_col<C>(N, pairq<C>(i, j), kn), lmq[jj], muq[jj]);
             }
         }
-        const double cc_mu_i = pr.has_colcost ? sel_player<P>(pr.cc_mu, i, [](int q) { return q; }) : 0.0;
-        const double cc_rad_i = pr.has_colcost ? sel_player<P>(pr.cc_radius, i, [](int q) { return q; }) : 0.0;
+        const double cc_mu_i = pr.has_colcost ? scen_player<C, P>(pr, G, pr.cc_mu, SC_CCM, i, [](int q) { return q; }) : 0.0;
+        const double cc_rad_i = pr.has_colcost ? scen_player<C, P>(pr, G, pr.cc_radius, SC_CCR, i, [](int q) { return q; }) : 0.0;
         const unsigned ca_mask_i = sel_player<P>(pr.ca_mask, i, [](int q) { return q; });
 #endif
 #pragma unroll
@@ -160,7 +174,7 @@ __device__ __forceinline__ void phase_a_pos_item(CPR pr, const Game& G, int N, i
 #if ALG_R6_PHASEA
                     const double nrm = sqrt(s2), mu = cc_mu_i, rad = cc_rad_i;
 #else
-                    const double nrm = sqrt(s2), mu = pr.cc_mu[i], rad = pr.cc_radius[i];
+                    const double nrm = sqrt(s2), mu = ALG_SCEN_AT(C, pr, G, cc_mu, SC_CCM, i), rad = ALG_SCEN_AT(C, pr, G, cc_radius, SC_CCR, i);
 #endif
                     if (fmax(0.0, rad - nrm) > 0.0) {
                         const double eps = 1e-10, eps_norm = eps * sqrt((double)n);
@@ -175,10 +189,10 @@ __device__ __forceinline__ void phase_a_pos_item(CPR pr, const Game& G, int N, i
                 }
                 if (pr.has_colavoid) {                                   // CollisionConstraint + AL expansion
 #if ALG_R6_PHASEA
-                    const double Rr = sel_player<P>(pr.ca_pair_r, i, [jj](int q) { return q * MAXP + (jj < q ? jj : jj + 1); });
+                    const double Rr = scen_player<C, P>(pr, G, pr.ca_pair_r, SC_CAR, i, [jj](int q) { return q * MAXP + (jj < q ? jj : jj + 1); });
                     const double on = (double)((ca_mask_i >> j) & 1u);                        // 0: this ordered pair carries no constraint
 #else
-                    const double Rr = pr.ca_pair_r[i * MAXP + j];
+                    const double Rr = ALG_SCEN_AT(C, pr, G, ca_pair_r, SC_CAR, i * MAXP + j);
                     const double on = (double)((pr.ca_mask[i] >> j) & 1u);                    // 0: this ordered pair carries no constraint
 #endif
                     double s2c = s2;
@@ -237,7 +251,7 @@ __device__ __forceinline__ void phase_a_pos_item(CPR pr, const Game& G, int N, i
                 }
                 if (MODE == 2) G.vals(pr)[ci] = c; if (!IBR || i == ip) acc.vsta = fmax(acc.vsta, fmax(0.0, c));
             };
-            const double* Wc = ext_walls(pr, pr.extc); const double* Cc = ext_circs(pr, pr.extc);
+            const double* Wc = ext_walls(pr, scen_ext(pr, G)); const double* Cc = ext_circs(pr, scen_ext(pr, G));
             const unsigned wmask = pr.wall_mask[i], cmask = pr.circ_mask[i];
             for (int wq = 0; wq < pr.nwall; wq++) {
                 double g[PD] = {}; const double on = (double)((wmask >> wq) & 1u);
@@ -250,7 +264,7 @@ __device__ __forceinline__ void phase_a_pos_item(CPR pr, const Game& G, int N, i
                 al_row(ext_circ_row(pr, i, k, cq), c, g);
             }
             if constexpr (PD == 3) {
-                const double* W3 = ext_walls3(pr, pr.extc); const double* Yc = ext_cyls(pr, pr.extc);
+                const double* W3 = ext_walls3(pr, scen_ext(pr, G)); const double* Yc = ext_cyls(pr, scen_ext(pr, G));
                 const unsigned w3mask = pr.wall3_mask[i], cymask = pr.cyl_mask[i];
                 for (int wq = 0; wq < pr.nwall3; wq++) {
                     double g[3]; const double on = (double)((w3mask >> wq) & 1u);
@@ -463,7 +477,7 @@ __device__ void assemble_pass(CPR pr0, const Game& G0, AsmLds<C>& L, int zsel, i
 #pragma unroll
                     for (int half = 0; half < 2; half++) {
                         const int ci = ext_sb_row(pr, i, k, half * n + a);
-                        const double cv = half == 0 ? xa - ext_sbmax(pr, pr.extc)[ei] : ext_sbmin(pr, pr.extc)[ei] - xa;
+                        const double cv = half == 0 ? xa - ext_sbmax(pr, scen_ext(pr, G))[ei] : ext_sbmin(pr, scen_ext(pr, G))[ei] - xa;
                         if (MODE == 2) G.vals(pr)[ci] = cv;
                         if (isfinite(cv)) {
                             const double lm = gld(G.lam(pr), ci), am = al_active_mu(cv, lm, gld(G.mu(pr), ci));
@@ -499,7 +513,7 @@ __device__ void assemble_pass(CPR pr0, const Game& G0, AsmLds<C>& L, int zsel, i
 #pragma unroll
                 for (int half = 0; half < 2; half++) {
                     const int ci = con_ctl<C>(pr, k, half * m + c);
-                    const double cv = half == 0 ? u - pr.umax[c] : pr.umin[c] - u;
+                    const double cv = half == 0 ? u - ALG_SCEN_AT(C, pr, G, umax, SC_UMAX, c) : ALG_SCEN_AT(C, pr, G, umin, SC_UMIN, c) - u;
                     if (MODE == 2) G.vals(pr)[ci] = cv;
                     if (isfinite(cv)) {
                         const double lm = gld(G.lam(pr), ci), am = al_active_mu(cv, lm, gld(G.mu(pr), ci));
@@ -872,7 +886,7 @@ __device__ void assemble_fused(CPR pr0, const Game& G0, AsmLds<C>& L, double alp
 #pragma unroll
                 for (int half = 0; half < 2; half++) {
                     const int ci = con_ctl<C>(pr, k, half * m + c);
-                    const double cv = half == 0 ? u - pr.umax[c] : pr.umin[c] - u;
+                    const double cv = half == 0 ? u - ALG_SCEN_AT(C, pr, G, umax, SC_UMAX, c) : ALG_SCEN_AT(C, pr, G, umin, SC_UMIN, c) - u;
                     if (DUAL && dual) {
                         // evaluate! + dual_update! (alpha_dual) + penalty_update! of the two control-bound rows of this control (dual_penalty_update's expressions;
                         // penalty_update! scales mu of every row, finite or not)
@@ -1063,7 +1077,7 @@ __device__ void trial_norms_multi(CPR pr0, const Game& G0, const double* lz, dou
                     const double dl0 = dl[0], dl1 = dl[1];
                     const double s2 = pair_dist2(dl0, dl1);
                     if (pr.has_colcost) {
-                        const double nrm = sqrt(s2), mu = pr.cc_mu[i], rad = pr.cc_radius[i];
+                        const double nrm = sqrt(s2), mu = ALG_SCEN_AT(C, pr, G, cc_mu, SC_CCM, i), rad = ALG_SCEN_AT(C, pr, G, cc_radius, SC_CCR, i);
                         if (fmax(0.0, rad - nrm) > 0.0) {
                             const double eps = 1e-10, eps_norm = eps * sqrt((double)n);
                             const double g0 = mu * (rad * (eps + dl0) / (eps_norm + nrm) - dl0);
@@ -1072,7 +1086,7 @@ __device__ void trial_norms_multi(CPR pr0, const Game& G0, const double* lz, dou
                         }
                     }
                     if (pr.has_colavoid) {
-                        const double Rr = pr.ca_pair_r[i * MAXP + j];
+                        const double Rr = ALG_SCEN_AT(C, pr, G, ca_pair_r, SC_CAR, i * MAXP + j);
                         const double on = (double)((pr.ca_mask[i] >> j) & 1u);
                         const double c = ca_value(on, Rr, s2);
                         const int ci = con_col<C>(N, pairq<C>(i, j), kn);
@@ -1146,7 +1160,7 @@ __device__ void trial_norms_multi(CPR pr0, const Game& G0, const double* lz, dou
             if (pr.has_ctl) {
 #pragma unroll
                 for (int half = 0; half < 2; half++) {
-                    const double cv = half == 0 ? u - pr.umax[c] : pr.umin[c] - u;
+                    const double cv = half == 0 ? u - ALG_SCEN_AT(C, pr, G, umax, SC_UMAX, c) : ALG_SCEN_AT(C, pr, G, umin, SC_UMIN, c) - u;
                     if (isfinite(cv)) {
                         const double lm = lmc[half], am = al_active_mu(cv, lm, muc[half]);
                         const double wl = lm + am * cv;

@@ -93,13 +93,21 @@ struct Params {
     // LQR block [Qd (p ni) | xf (p ni) | Rd (p mi) | uf (p mi)] (compact, own indices): per game (lqr_stride > 0) or shared (0)
     const double* lqr;
     int lqr_stride;
-    // constants of the extended constraints, shared by all games:
-    // [x_max (p n) | x_min (p n) | walls x1 y1 x2 y2 xv yv (6 ALG_MAX_WALLS) | circles xc yc r (3 ALG_MAX_CIRCLES)
-    //  | 3-D walls p1 p2 p3 v (12 per wall, ALG_MAX_WALLS) | cylinders p (3) axis l r (6 per cylinder, ALG_MAX_CIRCLES)]
-    const double* extc;
+    int scen_stride;        // doubles per game of `scen` below (a multiple of 16: 128-byte aligned blocks), 0 = one image shared by all games
+    // scenario blocks (read by the EXT instantiations only; the base ones read the fields above): per game (scen_stride > 0,
+    // alg_set_scenario_data) or one shared image (scen_stride = 0); layout at the SC_* offsets below.  (scen_stride sits in the
+    // padding behind lqr_stride: the base kernels see the Params layout they always had.)
+    const double* scen;
     alg_record* hist;       // B x hist_max Statistics records
     int* ho_queue;          // straggler hand-off (alg_set_handoff): [count | game indices of the parked games] (B + 1 ints; nullptr while the feature is off)
 };
+// Scenario block (doubles): the constraint and collision-cost numbers that may differ between the games of a handle.  The structure
+// (which constraints exist, table sizes, masks, cylinder axes, the +-inf pattern of the bounds) stays in Params.
+//   [ca_pair_r (MAXP x MAXP) | cc_radius (MAXP) | cc_mu (MAXP) | umax (MAXM) | umin (MAXM) | extended table:
+//    x_max (p n) | x_min (p n) | walls x1 y1 x2 y2 xv yv (6 ALG_MAX_WALLS) | circles xc yc r (3 ALG_MAX_CIRCLES)
+//    | 3-D walls p1 p2 p3 v (12 per wall, ALG_MAX_WALLS) | cylinders p (3) axis l r (6 per cylinder, ALG_MAX_CIRCLES)]
+constexpr int SC_CAR = 0, SC_CCR = SC_CAR + MAXP * MAXP, SC_CCM = SC_CCR + MAXP, SC_UMAX = SC_CCM + MAXP, SC_UMIN = SC_UMAX + MAXM, SC_EXT = SC_UMIN + MAXM;
+__host__ __device__ constexpr int scen_ext_len(int p, int n) { return 2 * p * n + 6 * ALG_MAX_WALLS + 3 * ALG_MAX_CIRCLES + 12 * ALG_MAX_WALLS + 6 * ALG_MAX_CIRCLES; }
 
 // The handle's parameters are read straight from the kernel-argument segment (constant address space, scalar loads): the
 // kernels take `Params` by value as their FIRST argument and the device code refers to it through this reference type, never
@@ -750,7 +758,15 @@ struct Game {
     __device__ __forceinline__ const double* Rd(CPR pr) const { return Qd(pr) + 2 * pr.p * pr.ni; }
     __device__ __forceinline__ const double* uf(CPR pr) const { return Qd(pr) + 2 * pr.p * pr.ni + pr.p * pr.mi; }
     __device__ __forceinline__ alg_record* hist(CPR pr) const { return as_global(pr.hist) + (size_t)g * pr.hist_max; }
+    // this game's scenario block (EXT instantiations; g is wave-uniform, so every read of it is a uniform-address load)
+    __device__ __forceinline__ const double* scen(CPR pr) const { return as_global(pr.scen) + (size_t)g * pr.scen_stride; }
 };
+// A scenario number: from the game's block in the EXT instantiations, from the handle's Params in the base ones.  (A macro: the base
+// instantiations keep the very expression `pr.field[idx]` they always had -- a helper taking the field's address compiled to a
+// different instruction schedule of the base kernels.)
+#define ALG_SCEN_AT(C, pr, G, field, off, idx) ((C::EXT) ? (G).scen(pr)[(off) + (idx)] : (pr).field[idx])
+// the game's extended-constraint table (the `ec` argument of ext_sbmax .. ext_cyls)
+__device__ __forceinline__ const double* scen_ext(CPR pr, const Game& G) { return G.scen(pr) + SC_EXT; }
 __device__ __forceinline__ Game game_view(CPR pr, int g) {
     Game G;
     G.base = as_global(pr.arena) + (size_t)g * pr.stride; G.g = g;

@@ -156,8 +156,12 @@ struct Handle {
     alg_step_info* d_info = nullptr;
     alg_record* d_rec = nullptr;
     double* d_lqr = nullptr;      // B x lqr_block (sized for the per-game case)
-    double* d_extc = nullptr;
-    std::vector<double> extc;     // host copy of pr.extc
+    std::vector<double> extc;     // extended-constraint table of the handle (the SC_EXT part of its scenario block)
+    double* d_scen = nullptr;     // shared scenario image (one block: Params values + extc), read by the EXT kernels
+    double* d_scen_games = nullptr;   // B blocks while some kind holds per-game values (alg_set_scenario_data)
+    std::vector<double> scen_games;   // ... host copy (B x scen_stride)
+    int scen_stride = 0;          // doubles per block (pad16 of the block length)
+    unsigned scen_kinds = 0;      // bit k: kind k holds per-game values
     int waves_per_game = 0;       // 0 = automatic (alg_set_waves_per_game)
     int handoff = 0;              // straggler hand-off budget (alg_set_handoff; 0 = off)
     int* d_ho = nullptr;          // its queue [count | game indices] (B + 1 ints)
@@ -355,9 +359,10 @@ int alloc_all(Handle* hd) {
     if ((rc = alloc_con(hd))) return rc;
     p.hist = nullptr;
     if ((rc = ensure_hist(hd, (long long)p.opt.outer_iter * p.opt.inner_iter + 1))) return rc;
-    hd->extc.assign(2 * (size_t)p.p * p.n + 6 * ALG_MAX_WALLS + 3 * ALG_MAX_CIRCLES + 12 * ALG_MAX_WALLS + 6 * ALG_MAX_CIRCLES, 0.0);
-    if ((rc = dalloc(hd, &hd->d_extc, hd->extc.size(), "extended-constraint constants"))) return rc;
-    p.extc = hd->d_extc;
+    hd->extc.assign((size_t)scen_ext_len(p.p, p.n), 0.0);
+    hd->scen_stride = pad16(SC_EXT + (int)hd->extc.size());
+    if ((rc = dalloc(hd, &hd->d_scen, (size_t)hd->scen_stride, "scenario block (shared)"))) return rc;
+    p.scen = hd->d_scen; p.scen_stride = 0;
     if ((rc = dalloc(hd, &hd->d_tmp, 2 * B, "d_tmp"))) return rc;
     if ((rc = dalloc(hd, &hd->d_itmp, B, "d_itmp"))) return rc;
     if ((rc = dalloc(hd, &hd->d_info, B, "d_info"))) return rc;
@@ -578,19 +583,40 @@ void set_all_pairs(Params& p, const double* radius) {
 }
 static int need_3d(Handle* hd, const char* who);
 static int ext_commit(Handle* hd);
+// The handle's shared scenario image: the Params values and the extended-constraint table at the SC_* offsets of algames_device.hpp
+static void scen_image(const Handle* hd, double* blk) {
+    const Params& p = hd->pr;
+    for (int e = 0; e < hd->scen_stride; e++) blk[e] = 0.0;
+    for (int e = 0; e < MAXP * MAXP; e++) blk[SC_CAR + e] = p.ca_pair_r[e];
+    for (int e = 0; e < MAXP; e++) { blk[SC_CCR + e] = p.cc_radius[e]; blk[SC_CCM + e] = p.cc_mu[e]; }
+    for (int e = 0; e < MAXM; e++) { blk[SC_UMAX + e] = p.umax[e]; blk[SC_UMIN + e] = p.umin[e]; }
+    for (size_t e = 0; e < hd->extc.size(); e++) blk[SC_EXT + e] = hd->extc[e];
+}
+// After every adder of an EXT handle: the shared image is uploaded again and any per-game scenario data is dropped (the kernels read
+// the shared image from then on).  Nothing to do for a base handle: its kernels read Params.
+static int scen_commit(Handle* hd) {
+    Params& p = hd->pr;
+    hd->scen_kinds = 0;
+    p.scen = hd->d_scen; p.scen_stride = 0;
+    if (!p.ext) return ALG_OK;
+    int rc = use_device(hd); if (rc) return rc;
+    std::vector<double> img((size_t)hd->scen_stride);
+    scen_image(hd, img.data());
+    return h2d(hd, hd->d_scen, img.data(), sizeof(double) * img.size());
+}
 int alg_add_collision_cost(alg_handle* h, const double* radius, const double* mu) {
     NEED_HANDLE("alg_add_collision_cost");
     Params& p = H->pr;
-    if (!radius || !mu) { p.has_colcost = 0; return ALG_OK; }
+    if (!radius || !mu) { p.has_colcost = 0; return scen_commit(H); }
     for (int i = 0; i < p.p; i++) { p.cc_radius[i] = radius[i]; p.cc_mu[i] = mu[i]; }
-    p.has_colcost = 1; return ALG_OK;
+    p.has_colcost = 1; return scen_commit(H);
 }
 int alg_add_collision_avoidance(alg_handle* h, const double* radius) {
     NEED_HANDLE("alg_add_collision_avoidance");
     Params& p = H->pr;
-    if (!radius) { p.has_colavoid = 0; return ALG_OK; }
+    if (!radius) { p.has_colavoid = 0; return scen_commit(H); }
     set_all_pairs(p, radius);
-    p.has_colavoid = 1; p.ca_dim = 2; return ALG_OK;
+    p.has_colavoid = 1; p.ca_dim = 2; return scen_commit(H);
 }
 // add_collision_avoidance!(game_con, i, j, radius) (constraints_methods.jl:5-19): ONE ordered pair with its own radius
 int add_pair(Handle* hd, const char* who, int i, int j, double radius, int dim) {
@@ -606,7 +632,8 @@ int add_pair(Handle* hd, const char* who, int i, int j, double radius, int dim) 
 }
 int alg_add_collision_avoidance_pair(alg_handle* h, int32_t i, int32_t j, double radius) {
     NEED_HANDLE("alg_add_collision_avoidance_pair");
-    return add_pair(H, "alg_add_collision_avoidance_pair", i, j, radius, 2);
+    if (int rc = add_pair(H, "alg_add_collision_avoidance_pair", i, j, radius, 2)) return rc;
+    return scen_commit(H);
 }
 int alg_add_spherical_collision_avoidance_pair(alg_handle* h, int32_t i, int32_t j, double radius) {
     NEED_HANDLE("alg_add_spherical_collision_avoidance_pair");
@@ -617,7 +644,7 @@ int alg_add_spherical_collision_avoidance_pair(alg_handle* h, int32_t i, int32_t
 int alg_add_control_bound(alg_handle* h, const double* umax, const double* umin) {
     NEED_HANDLE("alg_add_control_bound");
     Params& p = H->pr;
-    if (!umax || !umin) { p.has_ctl = 0; return ALG_OK; }
+    if (!umax || !umin) { p.has_ctl = 0; return scen_commit(H); }
     if (p.m > MAXM) return fail(ALG_ERR_ARG, "alg_add_control_bound: m too large");
     for (int i = 0; i < p.m; i++) if (!(umax[i] >= umin[i])) return fail(ALG_ERR_ARG, "Upper bounds must be greater than or equal to lower bounds");
     for (int i = 0; i < p.m; i++) { p.umax[i] = umax[i]; p.umin[i] = umin[i]; }
@@ -632,7 +659,7 @@ int alg_add_control_bound(alg_handle* h, const double* umax, const double* umin)
             p.ibr_ctl_rows[i] = mask;
         }
     }
-    p.has_ctl = 1; return ALG_OK;
+    p.has_ctl = 1; return scen_commit(H);
 }
 
 // ---- extended ingredient set (examples/intro_example.jl): switches the handle to the EXT kernel instantiation ----------
@@ -646,7 +673,7 @@ static int ext_commit(Handle* hd) {
     recount_con(p);
     dfree(hd, p.con); p.con = nullptr;
     if ((rc = alloc_con(hd))) return rc;
-    if ((rc = h2d(hd, hd->d_extc, hd->extc.data(), sizeof(double) * hd->extc.size()))) return rc;
+    if ((rc = scen_commit(hd))) return rc;
     hipLaunchKernelGGL(k_reset_con, dim3(p.B), dim3(WAVE), 0, hd->stream, hd->pr);
     if ((rc = launch_check("k_reset_con"))) return rc;
     return sync(hd);
@@ -771,7 +798,7 @@ static int need_3d(Handle* hd, const char* who) {
 int alg_add_spherical_collision_avoidance(alg_handle* h, const double* radius) {
     if (!h) return fail(ALG_ERR_ARG, "alg_add_spherical_collision_avoidance: null handle");
     Params& p = H->pr;
-    if (!radius) { p.has_colavoid = 0; p.ca_dim = 2; return ALG_OK; }
+    if (!radius) { p.has_colavoid = 0; p.ca_dim = 2; return scen_commit(H); }
     if (int rc = need_3d(H, "alg_add_spherical_collision_avoidance")) return rc;
     set_all_pairs(p, radius);
     p.has_colavoid = 1; p.ca_dim = 3;
@@ -824,6 +851,124 @@ int alg_add_cylinder_constraint_player(alg_handle* h, int32_t player, int32_t nc
     for (int c = 0; c < nc; c++) { for (int a = 0; a < 3; a++) rows[6 * c + a] = pp[3 * c + a]; rows[6 * c + 3] = (double)axis[c]; rows[6 * c + 4] = l[c]; rows[6 * c + 5] = r[c]; }
     double* Y = H->extc.data() + 2 * p.p * p.n + 6 * ALG_MAX_WALLS + 3 * ALG_MAX_CIRCLES + 12 * ALG_MAX_WALLS;
     return add_table_rows(6, ALG_MAX_CIRCLES, H, "alg_add_cylinder_constraint_player", Y, rows.data(), nc, player, p.ncyl, p.cyl_mask);
+}
+// ---- per-game scenario data (alg_set_scenario_data) ---------------------------------------------------------------------
+// Block offsets of the per-game values of one kind, in the order of the caller's B x len arrays; empty = the kind was not added.
+static std::vector<int> scen_map(const Handle* hd, int kind) {
+    const Params& p = hd->pr;
+    std::vector<int> m;
+    const int ew = SC_EXT + 2 * p.p * p.n, ec = ew + 6 * ALG_MAX_WALLS, e3 = ec + 3 * ALG_MAX_CIRCLES, ey = e3 + 12 * ALG_MAX_WALLS;
+    switch (kind) {
+    case ALG_SCEN_COLLISION_RADIUS:
+        if (p.has_colavoid) for (int i = 0; i < p.p; i++) for (int j = 0; j < p.p; j++) m.push_back(SC_CAR + i * MAXP + j);
+        break;
+    case ALG_SCEN_COLLISION_COST:
+        if (p.has_colcost) { for (int i = 0; i < p.p; i++) m.push_back(SC_CCR + i); for (int i = 0; i < p.p; i++) m.push_back(SC_CCM + i); }
+        break;
+    case ALG_SCEN_CONTROL_BOUND:
+        if (p.has_ctl) { for (int c = 0; c < p.m; c++) m.push_back(SC_UMAX + c); for (int c = 0; c < p.m; c++) m.push_back(SC_UMIN + c); }
+        break;
+    case ALG_SCEN_STATE_BOUND:
+        if (p.ext && p.has_sb) for (int e = 0; e < 2 * p.p * p.n; e++) m.push_back(SC_EXT + e);
+        break;
+    case ALG_SCEN_WALL:
+        if (p.ext) for (int w = 0; w < p.nwall; w++) for (int f = 0; f < 6; f++) m.push_back(ew + f * ALG_MAX_WALLS + w);
+        break;
+    case ALG_SCEN_CIRCLE:
+        if (p.ext) for (int c = 0; c < p.ncirc; c++) for (int f = 0; f < 3; f++) m.push_back(ec + f * ALG_MAX_CIRCLES + c);
+        break;
+    case ALG_SCEN_WALL3D:
+        if (p.ext) for (int w = 0; w < p.nwall3; w++) for (int f = 0; f < 12; f++) m.push_back(e3 + 12 * w + f);
+        break;
+    case ALG_SCEN_CYLINDER:       // p (3) l r of each entry; the axis (field 3) stays handle-wide
+        if (p.ext) for (int c = 0; c < p.ncyl; c++) for (int f : {0, 1, 2, 4, 5}) m.push_back(ey + 6 * c + f);
+        break;
+    }
+    return m;
+}
+static bool scen_kind_ok(int kind) { return kind >= ALG_SCEN_COLLISION_RADIUS && kind <= ALG_SCEN_CYLINDER; }
+int alg_scenario_data_len(alg_handle* h, int32_t kind, int32_t* len) {
+    if (!h || !len) return fail(ALG_ERR_ARG, "alg_scenario_data_len: null argument");
+    if (!scen_kind_ok(kind)) return fail(ALG_ERR_ARG, "alg_scenario_data_len: unknown kind");
+    *len = (int32_t)scen_map(H, kind).size();
+    return ALG_OK;
+}
+int alg_get_scenario_data(alg_handle* h, int32_t kind, double* data) {
+    if (!h || !data) return fail(ALG_ERR_ARG, "alg_get_scenario_data: null argument");
+    if (!scen_kind_ok(kind)) return fail(ALG_ERR_ARG, "alg_get_scenario_data: unknown kind");
+    const std::vector<int> map = scen_map(H, kind);
+    if (map.empty()) return fail(ALG_ERR_STATE, "alg_get_scenario_data: this kind of constraint / cost was not added to the handle");
+    std::vector<double> img((size_t)H->scen_stride);
+    scen_image(H, img.data());
+    const bool per = (H->scen_kinds >> kind) & 1u;
+    const size_t L = map.size();
+    for (int g = 0; g < H->pr.B; g++) {
+        const double* blk = per ? H->scen_games.data() + (size_t)g * H->scen_stride : img.data();
+        for (size_t e = 0; e < L; e++) data[g * L + e] = blk[map[e]];
+    }
+    return ALG_OK;
+}
+int alg_set_scenario_data(alg_handle* h, int32_t kind, const double* data) {
+    static const char* who = "alg_set_scenario_data";
+    if (!h) return fail(ALG_ERR_ARG, "alg_set_scenario_data: null handle");
+    if (!scen_kind_ok(kind)) return fail(ALG_ERR_ARG, "alg_set_scenario_data: unknown kind");
+    Params& p = H->pr;
+    const std::vector<int> map = scen_map(H, kind);
+    if (map.empty()) return fail(ALG_ERR_STATE, "alg_set_scenario_data: this kind of constraint / cost was not added to the handle");
+    const size_t L = map.size(), SS = (size_t)H->scen_stride;
+    std::vector<double> img(SS);
+    scen_image(H, img.data());
+    int rc = use_device(H); if (rc) return rc;
+    if (!data) {                  // back to the shared values
+        if (!((H->scen_kinds >> kind) & 1u)) return ALG_OK;
+        H->scen_kinds &= ~(1u << kind);
+        if (!H->scen_kinds) { p.scen = H->d_scen; p.scen_stride = 0; return ALG_OK; }
+        for (int g = 0; g < p.B; g++) for (size_t e = 0; e < L; e++) H->scen_games[g * SS + map[e]] = img[map[e]];
+        return h2d(H, H->d_scen_games, H->scen_games.data(), sizeof(double) * SS * p.B);
+    }
+    // validation of every game before anything changes
+    const bool bounds = kind == ALG_SCEN_CONTROL_BOUND || kind == ALG_SCEN_STATE_BOUND;
+    for (int g = 0; g < p.B; g++) {
+        const double* v = data + (size_t)g * L;
+        auto bad = [&](const std::string& what, size_t e) {
+            return fail(ALG_ERR_ARG, std::string(who) + ": game " + std::to_string(g) + ", entry " + std::to_string(e) + ": " + what);
+        };
+        for (size_t e = 0; e < L; e++) {
+            const double s0 = img[map[e]];
+            if (kind == ALG_SCEN_COLLISION_RADIUS) {
+                const int i = (int)e / p.p, j = (int)e % p.p;
+                if (i == j || !((p.ca_mask[i] >> j) & 1u)) continue;        // diagonal / pair never added: ignored
+                if (!(v[e] > 0.0) || !std::isfinite(v[e])) return bad("the radius of a pair must be positive and finite", e);
+                continue;
+            }
+            if (bounds) {
+                if (std::isfinite(s0) != std::isfinite(v[e]) || (!std::isfinite(s0) && !(s0 == v[e])))
+                    return bad("the +-inf pattern of the bounds differs from the handle's", e);
+                continue;
+            }
+            if (std::isfinite(s0) && !std::isfinite(v[e])) return bad("non-finite value where the handle's is finite", e);
+            if ((kind == ALG_SCEN_CIRCLE && e % 3 == 2) || (kind == ALG_SCEN_CYLINDER && e % 5 == 4))
+                if (!(v[e] > 0.0)) return bad("radius must be positive", e);
+        }
+        if (bounds) for (size_t e = 0; e < L / 2; e++) if (!(v[e] >= v[L / 2 + e])) return bad("Upper bounds must be greater than or equal to lower bounds", e);
+    }
+    // the first per-game call of a base handle switches it to the EXT instantiation (multipliers re-created like every extended adder)
+    if (!p.ext && (rc = ext_commit(H))) return rc;
+    if (!H->scen_kinds) {
+        if (!H->d_scen_games && (rc = dalloc(H, &H->d_scen_games, SS * p.B, "scenario blocks (per game)"))) return rc;
+        H->scen_games.resize(SS * p.B);
+        for (int g = 0; g < p.B; g++) std::copy(img.begin(), img.end(), H->scen_games.begin() + g * SS);
+    }
+    for (int g = 0; g < p.B; g++) {
+        for (size_t e = 0; e < L; e++) {
+            if (kind == ALG_SCEN_COLLISION_RADIUS) { const int i = (int)e / p.p, j = (int)e % p.p; if (i == j || !((p.ca_mask[i] >> j) & 1u)) continue; }
+            H->scen_games[g * SS + map[e]] = data[(size_t)g * L + e];
+        }
+    }
+    if ((rc = h2d(H, H->d_scen_games, H->scen_games.data(), sizeof(double) * SS * p.B))) return rc;
+    H->scen_kinds |= 1u << kind;
+    p.scen = H->d_scen_games; p.scen_stride = (int)SS;
+    return ALG_OK;
 }
 int alg_get_con_len(alg_handle* h, int32_t* n) {
     if (!h || !n) return fail(ALG_ERR_ARG, "alg_get_con_len: null argument");

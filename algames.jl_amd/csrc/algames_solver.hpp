@@ -241,7 +241,7 @@ __device__ void dual_penalty_update(CPR pr0, const Game& G0) {
             constexpr int PM1 = P > 1 ? P - 1 : 1;
             const int q = e / (N - 1), k = e % (N - 1) + 1, i = q / PM1, jj = q % PM1, j = jj < i ? jj : jj + 1;
             const double* x = zstate<C>(z, k);
-            const double d0 = x[i] - x[j], d1 = x[P + i] - x[P + j], R = pr.ca_pair_r[i * MAXP + j];
+            const double d0 = x[i] - x[j], d1 = x[P + i] - x[P + j], R = ALG_SCEN_AT(C, pr, G, ca_pair_r, SC_CAR, i * MAXP + j);
             double s2 = pair_dist2(d0, d1);
             if constexpr (C::PD == 3) { const double d2 = pr.ca_dim == 3 ? x[2 * P + i] - x[2 * P + j] : 0.0; s2 = __builtin_fma(d2, d2, s2); }
             const double c = ca_value((double)((pr.ca_mask[i] >> j) & 1u), R, s2);      // (the roundings of assemble_phase_a: its DUAL form performs this very update)
@@ -253,7 +253,7 @@ __device__ void dual_penalty_update(CPR pr0, const Game& G0) {
         for (int e = tid; e < pr.ctl_len; e += C::NT) {
             const int k = e / (2 * m), row = e % (2 * m), c = row % m;
             const double u = z[n + hu<C>(k, 0) + uoff<C>(c)];
-            const double cv = row < m ? u - pr.umax[c] : pr.umin[c] - u;
+            const double cv = row < m ? u - ALG_SCEN_AT(C, pr, G, umax, SC_UMAX, c) : ALG_SCEN_AT(C, pr, G, umin, SC_UMIN, c) - u;
             const int ci = pr.col_len + e;
             G.vals(pr)[ci] = cv;
             if (isfinite(cv)) G.lam(pr)[ci] = dual_ascent(G.lam(pr)[ci], o.alpha_dual, G.mu(pr)[ci], cv, o.lambda_max);
@@ -267,15 +267,15 @@ __device__ void dual_penalty_update(CPR pr0, const Game& G0) {
             if (e < pr.sb_len) {
                 const int row = e % (2 * n); k = (e / (2 * n)) % K; i = e / (2 * n * K);
                 const double* x = zstate<C>(z, k + 1);
-                c = row < n ? x[row] - ext_sbmax(pr, pr.extc)[i * n + row] : ext_sbmin(pr, pr.extc)[i * n + row - n] - x[row - n];
+                c = row < n ? x[row] - ext_sbmax(pr, scen_ext(pr, G))[i * n + row] : ext_sbmin(pr, scen_ext(pr, G))[i * n + row - n] - x[row - n];
             } else if (e < pr.sb_len + pr.wall_len) {
                 const int e2 = e - pr.sb_len, w = e2 % pr.nwall; k = (e2 / pr.nwall) % K; i = e2 / (pr.nwall * K);
                 const double* x = zstate<C>(z, k + 1); double gx, gy;
-                c = (double)((pr.wall_mask[i] >> w) & 1u) * wall_val(ext_walls(pr, pr.extc), w, x[i], x[P + i], &gx, &gy);
+                c = (double)((pr.wall_mask[i] >> w) & 1u) * wall_val(ext_walls(pr, scen_ext(pr, G)), w, x[i], x[P + i], &gx, &gy);
             } else if (e < pr.sb_len + pr.wall_len + pr.circ_len) {
                 const int e2 = e - pr.sb_len - pr.wall_len, cq = e2 % pr.ncirc; k = (e2 / pr.ncirc) % K; i = e2 / (pr.ncirc * K);
                 const double* x = zstate<C>(z, k + 1); double gx, gy;
-                c = (double)((pr.circ_mask[i] >> cq) & 1u) * circ_val(ext_circs(pr, pr.extc), cq, x[i], x[P + i], &gx, &gy);
+                c = (double)((pr.circ_mask[i] >> cq) & 1u) * circ_val(ext_circs(pr, scen_ext(pr, G)), cq, x[i], x[P + i], &gx, &gy);
             } else {
                 i = 0; k = 0; c = 0.0;
                 if constexpr (C::PD == 3) {
@@ -286,7 +286,7 @@ __device__ void dual_penalty_update(CPR pr0, const Game& G0) {
                     const double* x = zstate<C>(z, k + 1);
                     const double pos[3] = {x[i], x[P + i], x[2 * P + i]}; double g[3];
                     const double on = (double)(((w3 ? pr.wall3_mask[i] : pr.cyl_mask[i]) >> q) & 1u);
-                    c = on * (w3 ? wall3_val(ext_walls3(pr, pr.extc), q, pos, g) : cyl_val(ext_cyls(pr, pr.extc), q, pos, g));
+                    c = on * (w3 ? wall3_val(ext_walls3(pr, scen_ext(pr, G)), q, pos, g) : cyl_val(ext_cyls(pr, scen_ext(pr, G)), q, pos, g));
                 }
             }
             const int ci = e0 + e;

@@ -278,13 +278,16 @@ class GameObjective:
 
 
 def add_collision_cost(game_obj, radius, μ):
-    """add_collision_cost!(game_obj, radius, μ), objective.jl:84-100 (one set per objective)."""
+    """add_collision_cost!(game_obj, radius, μ), objective.jl:84-100 (one set per objective).  `radius` and `μ` are (p,) or, for
+    a batch whose games differ in them, (B, p) like the per-game LQR data of GameObjective."""
     p = game_obj.probsize.p
-    assert p == len(radius) == len(μ)
+    radius, μ = np.asarray(radius, dtype=np.float64), np.asarray(μ, dtype=np.float64)
+    if radius.shape != μ.shape or radius.ndim not in (1, 2) or radius.shape[-1] != p:
+        raise ValueError(f"add_collision_cost: radius and μ must both be (p,) or (B, p) with p = {p}")
     if game_obj.collision_radius is not None:
         raise AlgamesError("only one collision-cost set per GameObjective is supported")
-    game_obj.collision_radius = np.asarray(radius, dtype=np.float64)
-    game_obj.collision_μ = np.asarray(μ, dtype=np.float64)
+    game_obj.collision_radius = radius
+    game_obj.collision_μ = μ
 
 
 # --------------------------------------------------------------------------------------------------
@@ -594,15 +597,186 @@ def _print_history(prob):
 # --------------------------------------------------------------------------------------------------
 # GameProblem (src/problem/problem.jl:19-53)
 # --------------------------------------------------------------------------------------------------
+# --------------------------------------------------------------------------------------------------
+# Batches of differing scenarios: per-game constraint / collision-cost numbers (alg_set_scenario_data)
+# --------------------------------------------------------------------------------------------------
+def _inf_pattern(a):
+    a = np.asarray(a, dtype=np.float64)
+    return tuple(np.where(np.isinf(a), np.sign(a), 0.0).tolist())
+
+
+def scenario_structure(game_con):
+    """What a batch's games must share: the (field, value) list of one GameConstraintValues, in a fixed order.  The numbers (radii,
+    bounds, wall / circle / cylinder data) are not part of it, except the +-inf pattern of the bounds and the cylinder axes."""
+    gc = game_con
+    plen = lambda d: tuple((i, len(d[i]) if not isinstance(d[i], tuple) else len(d[i][0])) for i in sorted(d))
+    return [
+        ("collision avoidance (all pairs)", gc.collision_radius is not None),
+        ("collision avoidance pairs", tuple(sorted(gc.collision_pairs))),
+        ("spherical collision avoidance", bool(gc.spherical)),
+        ("control bound", gc.u_max is not None),
+        ("control bound +-inf pattern", None if gc.u_max is None else (_inf_pattern(gc.u_max), _inf_pattern(gc.u_min))),
+        ("state bound players", tuple(sorted(gc.state_bounds))),
+        ("state bound +-inf pattern", tuple((_inf_pattern(gc.state_bounds[i][0]), _inf_pattern(gc.state_bounds[i][1])) for i in sorted(gc.state_bounds))),
+        ("walls", None if not gc.walls else len(gc.walls)),
+        ("circles", None if gc.circles is None else len(gc.circles[0])),
+        ("player walls", plen(gc.player_walls)),
+        ("player circles", plen(gc.player_circles)),
+        ("walls3d", None if not gc.walls3d else len(gc.walls3d)),
+        ("cylinders", None if not gc.cylinders else tuple(c.v for c in gc.cylinders)),
+        ("player walls3d", plen(gc.player_walls3d)),
+        ("player cylinders", tuple((i, tuple(c.v for c in gc.player_cylinders[i])) for i in sorted(gc.player_cylinders))),
+    ]
+
+
+def _player_table(per_player):
+    """The handle's table of distinct entries built from per-player lists the way alg_add_*_player builds it (players in increasing
+    order, an identical entry shared): (table rows, [(player, index in that player's list) of every row's first occurrence, ...])."""
+    rows, owners = [], []
+    for i in sorted(per_player):
+        for k, r in enumerate(per_player[i]):
+            r = tuple(r)
+            at = next((e for e, t in enumerate(rows) if t == r), None)
+            if at is None:
+                rows.append(r); owners.append([])
+                at = len(rows) - 1
+            owners[at].append((i, k))
+    return rows, owners
+
+
+def _wall_rows(ws):
+    return [(w.p1[0], w.p1[1], w.p2[0], w.p2[1], w.v[0], w.v[1]) for w in ws]
+
+
+def _wall3_rows(ws):
+    return [tuple(np.concatenate([w.p1, w.p2, w.p3, w.v]).tolist()) for w in ws]
+
+
+def _cyl_rows(cs):      # dedup key of the handle's table (p, axis, l, r); the per-game values drop the axis
+    return [(c.p[0], c.p[1], c.p[2], float(c.v), c.l, c.r) for c in cs]
+
+
+def _circle_rows(circ):
+    xc, yc, r = circ
+    return [(xc[k], yc[k], r[k]) for k in range(len(xc))]
+
+
+def scenario_data(game_cons, game_obj=None, every_kind=False):
+    """Per-game scenario data of a batch of GameConstraintValues (one per game) and an optional GameObjective whose collision
+    cost may be (B, p).  Checks that every game has game 0's structure (AlgamesError naming the first game and field that differ)
+    and returns {ALG_SCEN_* kind: (B, len) array} for the kinds whose numbers differ between the games; kinds equal for all games
+    are left out (the handle's shared values, from game 0, hold for them) unless `every_kind` is set.  GameProblem sets it: a
+    problem given per-game data runs on the EXT kernels whatever its games' numbers happen to be, so the arithmetic a game gets does
+    not depend on how a batch is split into shards.  Per-player walls / circles / 3-D walls / cylinders map
+    onto game 0's deduplicated table: a game that gives two players different values where game 0 shares one entry is rejected."""
+    from ._abi import (ALG_SCEN_COLLISION_RADIUS, ALG_SCEN_COLLISION_COST, ALG_SCEN_CONTROL_BOUND, ALG_SCEN_STATE_BOUND,
+                       ALG_SCEN_WALL, ALG_SCEN_CIRCLE, ALG_SCEN_WALL3D, ALG_SCEN_CYLINDER)
+    cons = list(game_cons)
+    B = len(cons)
+    g0 = cons[0]
+    p, n = g0.probsize.p, g0.probsize.n
+    s0 = scenario_structure(g0)
+    for g in range(1, B):
+        for (field, v0), (_, v) in zip(s0, scenario_structure(cons[g])):
+            if v != v0:
+                raise AlgamesError(f"game_con[{g}] differs from game_con[0] in its structure: {field} ({v} vs {v0}); "
+                                   "only the numbers may differ between the games of one batch")
+    out = {}
+
+    def table_values(get_rows, per_player_attr, all_attr, drop=None):
+        """(B, entries x fields) values of one table kind for every game, or None if the kind is absent"""
+        if getattr(g0, all_attr):
+            vals = [get_rows(getattr(gc, all_attr)) for gc in cons]
+        elif getattr(g0, per_player_attr):
+            rows0, owners = _player_table({i: get_rows(v) for i, v in getattr(g0, per_player_attr).items()})
+            vals = []
+            for g, gc in enumerate(cons):
+                pp = {i: get_rows(v) for i, v in getattr(gc, per_player_attr).items()}
+                rows = []
+                for e, own in enumerate(owners):
+                    r = tuple(pp[own[0][0]][own[0][1]])
+                    for (i, k) in own[1:]:
+                        if tuple(pp[i][k]) != r:
+                            raise AlgamesError(f"game_con[{g}]: players {own[0][0]} and {i} share entry {e} of the {per_player_attr} table "
+                                               "in game_con[0] but have different values here")
+                    rows.append(r)
+                vals.append(rows)
+        else:
+            return None
+        a = np.asarray(vals, dtype=np.float64)
+        if drop is not None:
+            a = np.delete(a, drop, axis=2)
+        return a.reshape(B, -1)
+
+    data = {}
+    if g0.collision_radius is not None or g0.collision_pairs:
+        a = np.zeros((B, p, p))
+        for g, gc in enumerate(cons):
+            if gc.collision_radius is not None:
+                r = np.broadcast_to(np.asarray(gc.collision_radius, dtype=np.float64), (p,))
+                a[g] = r[:, None] + r[None, :]
+                np.fill_diagonal(a[g], 0.0)
+            for (i, j), rad in gc.collision_pairs.items():
+                a[g, i - 1, j - 1] = rad
+        data[ALG_SCEN_COLLISION_RADIUS] = a.reshape(B, p * p)
+    if game_obj is not None and game_obj.collision_radius is not None:
+        r = np.broadcast_to(game_obj.collision_radius, (B, p)); mu = np.broadcast_to(game_obj.collision_μ, (B, p))
+        data[ALG_SCEN_COLLISION_COST] = np.concatenate([r, mu], axis=1)
+    if g0.u_max is not None:
+        data[ALG_SCEN_CONTROL_BOUND] = np.stack([np.concatenate([np.asarray(gc.u_max, dtype=np.float64), np.asarray(gc.u_min, dtype=np.float64)]) for gc in cons])
+    if g0.state_bounds:
+        a = np.empty((B, 2, p, n))
+        a[:, 0], a[:, 1] = np.inf, -np.inf
+        for g, gc in enumerate(cons):
+            for i, (mx, mn) in gc.state_bounds.items():
+                a[g, 0, i - 1], a[g, 1, i - 1] = mx, mn
+        data[ALG_SCEN_STATE_BOUND] = a.reshape(B, -1)
+    for kind, rows_fn, own, shared, drop in ((ALG_SCEN_WALL, _wall_rows, "player_walls", "walls", None),
+                                              (ALG_SCEN_CIRCLE, _circle_rows, "player_circles", "circles", None),
+                                              (ALG_SCEN_WALL3D, _wall3_rows, "player_walls3d", "walls3d", None),
+                                              (ALG_SCEN_CYLINDER, _cyl_rows, "player_cylinders", "cylinders", 3)):
+        a = table_values(rows_fn, own, shared, drop)
+        if a is not None:
+            data[kind] = a
+    for kind, a in data.items():
+        if every_kind or not all(np.array_equal(a[g], a[0]) for g in range(1, B)):
+            out[kind] = np.ascontiguousarray(a, dtype=np.float64)
+    return out
+
+
+def _obj_row(game_obj, g):
+    """game_obj with its (B, p) collision cost reduced to game g's row (the handle's shared values)"""
+    if game_obj.collision_radius is None or np.ndim(game_obj.collision_radius) == 1:
+        return game_obj
+    import copy
+    o = copy.copy(game_obj)
+    o.collision_radius, o.collision_μ = game_obj.collision_radius[g], game_obj.collision_μ[g]
+    return o
+
+
 class GameProblem:
     def __init__(self, N, dt, x0, model, opts, game_obj, game_con, backend=None, device=0, game_id0=0):
         self.probsize = ProblemSize(N, model)
-        self.model, self.opts, self.game_obj, self.game_con = model, opts, game_obj, game_con
-        self.dt = dt
         x0 = np.asarray(x0, dtype=np.float64)
         self.single = x0.ndim == 1
         self.x0 = np.ascontiguousarray(x0.reshape(-1, model.n))
         self.B = self.x0.shape[0]
+        # game_con: one GameConstraintValues for every game, or a sequence of B of them (same structure, numbers may differ)
+        self.game_cons = None
+        if not isinstance(game_con, GameConstraintValues):
+            self.game_cons = list(game_con)
+            if len(self.game_cons) != self.B:
+                raise ValueError(f"GameProblem: {len(self.game_cons)} game_con for a batch of {self.B} games")
+            game_con = self.game_cons[0]
+        cc = game_obj.collision_radius
+        if cc is not None and np.ndim(cc) == 2 and np.shape(cc)[0] != self.B:
+            raise ValueError(f"GameProblem: collision cost of {np.shape(cc)[0]} games for a batch of {self.B} games")
+        # per-game data given: every kind goes to the device, so any shard of the batch runs the EXT kernels like the whole batch
+        scen = scenario_data(self.game_cons or [game_con] * self.B, game_obj, every_kind=True) \
+            if (self.game_cons or (cc is not None and np.ndim(cc) == 2)) else {}
+        self.model, self.opts, self.game_obj, self.game_con = model, opts, game_obj, game_con
+        game_obj = _obj_row(game_obj, 0)
+        self.dt = dt
         self.game_id0 = game_id0
         lib = backend if backend is not None else hip_lib()
         self.batch = Batch(lib, model.model_id, model.p, N, dt, self.B, d=model.d, device=device)
@@ -649,8 +823,11 @@ class GameProblem:
         for i in sorted(game_con.player_cylinders):
             c = game_con.player_cylinders[i]
             self.batch.add_cylinder_constraint_player(i - 1, [a.p for a in c], [a.v for a in c], [a.l for a in c], [a.r for a in c])
+        for kind in sorted(scen):       # after every adder: an adder drops per-game data
+            self.batch.set_scenario_data(kind, scen[kind])
         self.stats = None
-        game_con.active_set_tolerance = opts.active_set_tolerance      # set_constraint_params!, game_constraints.jl:37
+        for gc in (self.game_cons or [game_con]):
+            gc.active_set_tolerance = opts.active_set_tolerance        # set_constraint_params!, game_constraints.jl:37
         self._sync_options()       # set_constraint_params!(game_con, opts), problem.jl:49
 
     def _sync_options(self):

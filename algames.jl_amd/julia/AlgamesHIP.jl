@@ -69,8 +69,10 @@ end
 
 """
 A batch of structurally identical `GameProblem`s bound to one device handle (`alg_create` ... `alg_destroy`).
-All problems must share model, N, dt, options and constraint structure (collision-avoidance radii, control / state bounds,
-walls, circles, collision cost); they may differ in x0 and in the LQR data.  The handle lives until `close(bp)` or finalisation,
+All problems must share model, N, dt, options and constraint structure (which constraints exist, the number of walls / circles /
+pairs, per-player sets, cylinder axes, the +-inf pattern of the bounds; `setup!` checks it and errors naming the first problem that
+differs); they may differ in x0, in the LQR data and in the constraint and collision-cost numbers (radii, bounds, obstacle positions),
+which are uploaded per game (`alg_set_scenario_data`) where they differ.  The handle lives until `close(bp)` or finalisation,
 so repeated solves (warm starts with `opts.dual_reset = false`, MPC loops) reuse the device buffers.
 """
 mutable struct BatchedGameProblem{P<:GameProblem}
@@ -178,10 +180,112 @@ function setup!(bp::BatchedGameProblem, device)
         check(ccall((:alg_add_control_bound, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), bp.h,
                     Vector(con.u_max), Vector(con.u_min)))
     end
+    # batches of differing scenarios: every problem must have problem 1's constraint structure; the numbers may differ per game
+    s1 = scenario_structure(prob)
+    for g in 2:B
+        sg = scenario_structure(probs[g])
+        sg == s1 || error("BatchedGameProblem: problem $g differs from problem 1 in its constraint structure (first difference: " *
+                          "$(first_difference(sg, s1))); only the numbers may differ between the games of one batch")
+    end
+    upload_scenarios!(bp)
     cl = Ref{Int32}(0)
     check(ccall((:alg_get_con_len, LIB), Cint, (Ptr{Cvoid}, Ref{Int32}), bp.h, cl))
     bp.con_len = cl[]
     return bp
+end
+
+# What the problems of one batch must share: the kinds of constraint per player and their counts, pair partners, cylinder axes, and
+# the +-inf pattern of the bounds (it decides which rows count).  The numbers themselves are not part of it.
+infpattern(v) = Tuple(isinf(x) ? sign(x) : 0.0 for x in v)
+function scenario_structure(prob)
+    ps = prob.probsize
+    s = Any[("collision cost", length(prob.game_obj.obj[1]) > 1)]
+    for i in 1:ps.p, cv in prob.game_con.state_conval[i]
+        con = cv.con
+        if con isa TO.CollisionConstraint
+            push!(s, ("collision avoidance", i, partner_of(ps, con), length(con.x1)))
+        elseif con isa Algames.StateBoundConstraint
+            push!(s, ("state bound", i, infpattern(con.x_max), infpattern(con.x_min)))
+        elseif con isa Algames.WallConstraint
+            push!(s, ("walls", i, length(con)))
+        elseif con isa TO.CircleConstraint
+            push!(s, ("circles", i, length(con)))
+        elseif con isa Algames.Wall3DConstraint
+            push!(s, ("3-D walls", i, length(con)))
+        elseif con isa Algames.CylinderConstraint
+            push!(s, ("cylinders", i, Tuple(con.v)))
+        end
+    end
+    if !isempty(prob.game_con.control_conval)
+        con = prob.game_con.control_conval[1].con
+        push!(s, ("control bound", infpattern(con.u_max), infpattern(con.u_min)))
+    end
+    return s
+end
+function first_difference(a, b)
+    length(a) == length(b) || return "number of constraint sets"
+    k = findfirst(q -> a[q] != b[q], eachindex(a))
+    return string(a[k][1], a[k] isa Tuple && length(a[k]) > 1 && a[k][2] isa Integer ? " of player $(a[k][2])" : "")
+end
+
+# Per-game values of one ALG_SCEN_* kind (include/algames_hip.h) for problem `pr`, laid out on problem 1's tables
+const SCEN_WALL, SCEN_CIRCLE, SCEN_WALL3D, SCEN_CYLINDER = 4, 5, 6, 7
+function scenario_values(bp::BatchedGameProblem, pr, kind::Integer, len::Integer)
+    prob1 = bp.probs[1]; ps = prob1.probsize; p, n, m = ps.p, ps.n, ps.m
+    v = zeros(len)
+    if kind == 0                                     # collision radius of ordered pair (i, j) at (i-1) p + j
+        for i in 1:p, cv in pr.game_con.state_conval[i]
+            cv.con isa TO.CollisionConstraint && (v[(i - 1) * p + partner_of(ps, cv.con)] = cv.con.radius)
+        end
+    elseif kind == 1                                 # collision cost: radius (p) | mu (p)
+        for i in 1:p
+            c = pr.game_obj.obj[i][2].cost[1]; v[i] = c.r; v[p + i] = c.μ
+        end
+    elseif kind == 2                                 # control bound: u_max (m) | u_min (m)
+        con = pr.game_con.control_conval[1].con
+        v[1:m] = con.u_max; v[m+1:2m] = con.u_min
+    elseif kind == 3                                 # state bound: x_max (p x n) | x_min (p x n); players without one: +-inf
+        v[1:p*n] .= Inf; v[p*n+1:2p*n] .= -Inf
+        for i in 1:p, cv in pr.game_con.state_conval[i]
+            cv.con isa Algames.StateBoundConstraint || continue
+            v[(i - 1) * n .+ (1:n)] = cv.con.x_max; v[p * n + (i - 1) * n .+ (1:n)] = cv.con.x_min
+        end
+    else                                             # tables: problem 1's entry of each conval row, pr's values of that row
+        walls, circs, walls3, cyls = constraint_tables(prob1)
+        T, key, tab, keep = kind == SCEN_WALL ? (Algames.WallConstraint, wall_key, walls, 1:6) :
+                            kind == SCEN_CIRCLE ? (TO.CircleConstraint, circ_key, circs, 1:3) :
+                            kind == SCEN_WALL3D ? (Algames.Wall3DConstraint, wall3_key, walls3, 1:12) :
+                            (Algames.CylinderConstraint, cyl_key, cyls, [1, 2, 3, 5, 6])      # the axis stays handle-wide
+        F = length(keep); seen = falses(length(tab))
+        for i in 1:p, (cv1, cvg) in zip(prob1.game_con.state_conval[i], pr.game_con.state_conval[i])
+            cv1.con isa T || continue
+            for r in 1:length(cv1.con)
+                t = findfirst(==(key(cv1.con, r)), tab)
+                val = Float64[key(cvg.con, r)[f] for f in keep]
+                if seen[t]
+                    v[(t - 1) * F .+ (1:F)] == val || error("BatchedGameProblem: problem 1 shares one table entry between players " *
+                                                            "that another problem gives different values")
+                end
+                v[(t - 1) * F .+ (1:F)] = val; seen[t] = true
+            end
+        end
+    end
+    return v
+end
+
+# Upload the kinds whose numbers differ between the problems (the handle holds problem 1's values for the others)
+function upload_scenarios!(bp::BatchedGameProblem)
+    B = length(bp.probs)
+    B > 1 || return nothing
+    for kind in 0:7
+        len = Ref{Int32}(0)
+        check(ccall((:alg_scenario_data_len, LIB), Cint, (Ptr{Cvoid}, Int32, Ref{Int32}), bp.h, kind, len))
+        len[] == 0 && continue
+        V = reduce(hcat, [scenario_values(bp, pr, kind, len[]) for pr in bp.probs])      # len x B = B x len game-major
+        all(g -> isequal(V[:, g], V[:, 1]), 2:B) && continue
+        check(ccall((:alg_set_scenario_data, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), bp.h, kind, V))
+    end
+    return nothing
 end
 
 # player j whose position indices a CollisionConstraint of player i points at (x2 = px[j] or pz[j][1:3])

@@ -32,7 +32,7 @@ class ShardedGameProblem:
         for (lo, hi), dev in zip(self.cuts, self.devices):
             if hi <= lo:
                 continue
-            self.shards.append(host.GameProblem(N, dt, x0[lo:hi], model, opts, _slice_obj(game_obj, lo, hi), game_con,
+            self.shards.append(host.GameProblem(N, dt, x0[lo:hi], model, opts, _slice_obj(game_obj, lo, hi), _slice_con(game_con, lo, hi),
                                                 backend=backend, device=dev, game_id0=game_id0 + lo))
         self.cuts = [c for c in self.cuts if c[1] > c[0]]
         # one kernel shape for all shards: the automatic choice depends on the batch size of a handle (team kernels for small
@@ -67,14 +67,25 @@ class ShardedGameProblem:
 
 
 def _slice_obj(obj, lo, hi):
-    if obj.Qdiag.ndim != 3:
+    per_cc = obj.collision_radius is not None and np.ndim(obj.collision_radius) == 2
+    if obj.Qdiag.ndim != 3 and not per_cc:
         return obj
     import copy
     o = copy.copy(obj)
-    o.Qdiag, o.Rdiag = obj.Qdiag[lo:hi], obj.Rdiag[lo:hi]
-    o.xf = obj.xf[lo:hi] if obj.xf.ndim == 3 else obj.xf
-    o.uf = obj.uf[lo:hi] if obj.uf.ndim == 3 else obj.uf
+    if obj.Qdiag.ndim == 3:
+        o.Qdiag, o.Rdiag = obj.Qdiag[lo:hi], obj.Rdiag[lo:hi]
+        o.xf = obj.xf[lo:hi] if obj.xf.ndim == 3 else obj.xf
+        o.uf = obj.uf[lo:hi] if obj.uf.ndim == 3 else obj.uf
+    if per_cc:       # per-game collision cost (B, p)
+        o.collision_radius, o.collision_μ = obj.collision_radius[lo:hi], obj.collision_μ[lo:hi]
     return o
+
+
+def _slice_con(game_con, lo, hi):
+    """one GameConstraintValues for every game, or the shard's part of a per-game list"""
+    if isinstance(game_con, host.GameConstraintValues):
+        return game_con
+    return list(game_con)[lo:hi]
 
 
 def newton_solve_sharded(prob, init=True):

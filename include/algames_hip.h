@@ -279,6 +279,33 @@ int alg_add_cylinder_constraint_player(alg_handle* h, int32_t player, int32_t n_
 /* current length of the constraint dual / penalty / value vectors of one game */
 int alg_get_con_len(alg_handle* h, int32_t* con_len);
 
+/* ---- per-game scenario data: the constraint and collision-cost NUMBERS may differ between the games of one handle.
+ * What stays handle-wide is the structure the adders above set: which kinds exist, how many walls / circles / 3-D walls /
+ * cylinders and pairs there are, the per-player masks, the cylinder axes and the +-inf pattern of the bounds (it decides the
+ * rows that count).  data is B x len, game-major; len = alg_scenario_data_len(kind).
+ *   - ALG_ERR_STATE if the kind was not added; ALG_ERR_ARG (nothing changes) if for any game: a value is non-finite where the
+ *     handle's is finite, the +-inf pattern of a bound differs from the handle's, u_max < u_min or x_max < x_min, or a radius
+ *     is <= 0 on a pair that exists, a circle or a cylinder.
+ *   - per-game data runs on the EXT kernel instantiations.  The first call on a handle that is not EXT yet switches it, which
+ *     re-creates the multipliers like every extended adder (lambda = 0, mu = rho_0); a configuration without an EXT
+ *     instantiation (DoubleIntegrator d = 1) gets ALG_ERR_ARG.  Later calls only upload values and leave lambda and mu alone
+ *     (an MPC caller may move obstacles between solves and keep the warm start).
+ *   - any later adder (alg_add_*) drops ALL per-game data of the handle: the games share the handle's values again.
+ *   - every entry point honours it: solves, the EXT team kernels (dense-direction configurations), the step-wise calls, IBR and
+ *     alg_mpc_solve.  The tile-path team kernels exist for the base instantiations only, so a tile-path handle with per-game
+ *     data runs the one-wavefront EXT kernels (e.g. the three-player double integrator at 64 MPC seeds). */
+#define ALG_SCEN_COLLISION_RADIUS 0  /* p*p: [i*p+j] = radius of ordered pair (i,j); diagonal and pairs never added are ignored */
+#define ALG_SCEN_COLLISION_COST   1  /* 2p: radius (p) | mu (p)                                                            */
+#define ALG_SCEN_CONTROL_BOUND    2  /* 2m: u_max (m) | u_min (m)                                                          */
+#define ALG_SCEN_STATE_BOUND      3  /* 2pn: x_max (p x n) | x_min (p x n), the extc order                                 */
+#define ALG_SCEN_WALL             4  /* 6 per table entry: x1 y1 x2 y2 xv yv                                               */
+#define ALG_SCEN_CIRCLE           5  /* 3 per table entry: xc yc r                                                         */
+#define ALG_SCEN_WALL3D           6  /* 12 per table entry: p1 p2 p3 v                                                     */
+#define ALG_SCEN_CYLINDER         7  /* 5 per table entry: p (3) l r   (the axis stays handle-wide)                        */
+int alg_scenario_data_len(alg_handle* h, int32_t kind, int32_t* len);     /* doubles per game; 0 if the kind was not added */
+int alg_set_scenario_data(alg_handle* h, int32_t kind, const double* data /* B x len, or NULL = back to the shared values */);
+int alg_get_scenario_data(alg_handle* h, int32_t kind, double* data /* B x len; the shared values repeated if not per game */);
+
 /* set_traj!/get_traj! (primal_dual_traj.jl:46-107) over the batch: B x traj_len.
  * (ALG_TRAJ_TRIAL after a solve: x_1 = x0; the rest is the library's scratch -- the line search accepts a trial by exchanging buffer
  * offsets, a solve that ends on the exchanged side copies pdtraj home: the trial buffer then holds pdtraj as in the reference, otherwise the iterate before it) */
