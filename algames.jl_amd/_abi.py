@@ -18,6 +18,9 @@ ALG_ERR_ARG, ALG_ERR_DEVICE, ALG_ERR_STATE = -1, -2, -3
 # kinds of per-game scenario data (alg_set_scenario_data)
 (ALG_SCEN_COLLISION_RADIUS, ALG_SCEN_COLLISION_COST, ALG_SCEN_CONTROL_BOUND, ALG_SCEN_STATE_BOUND,
  ALG_SCEN_WALL, ALG_SCEN_CIRCLE, ALG_SCEN_WALL3D, ALG_SCEN_CYLINDER) = range(8)
+# which kernels per-game data of the base kinds runs on (alg_set_scenario_kernels)
+ALG_SCEN_KERNELS_EXT, ALG_SCEN_KERNELS_BASE = 0, 1
+SCEN_KERNELS = ("ext", "base")
 SCEN_KINDS = ("collision_radius", "collision_cost", "control_bound", "state_bound", "wall", "circle", "wall3d", "cylinder")
 
 
@@ -144,10 +147,12 @@ SIGNATURES = {
     "scenario_data_len": (C.c_int, [_P, C.c_int32, _I]),
     "set_scenario_data": (C.c_int, [_P, C.c_int32, _D]),
     "get_scenario_data": (C.c_int, [_P, C.c_int32, _D]),
+    "set_scenario_kernels": (C.c_int, [_P, C.c_int32]),
+    "get_scenario_kernels": (C.c_int, [_P, _I, _I]),
 }
 # Entry points a backend may lack (the CPU oracle has no per-game scenario data): bound when present; calling one that is absent
 # raises AlgamesError naming the backend.
-OPTIONAL = frozenset({"scenario_data_len", "set_scenario_data", "get_scenario_data"})
+OPTIONAL = frozenset({"scenario_data_len", "set_scenario_data", "get_scenario_data", "set_scenario_kernels", "get_scenario_kernels"})
 
 
 class AlgamesError(RuntimeError):
@@ -450,6 +455,24 @@ class Batch:
         out = np.empty((self.B, L))
         self.lib.check(self.lib.get_scenario_data(self.h, k, _dptr(out)))
         return out
+
+    def set_scenario_kernels(self, which):
+        """Which kernels per-game data of the base kinds (pair radii, collision cost, control bounds) runs on: "ext" / ALG_SCEN_KERNELS_EXT
+        (default: the first set_scenario_data switches the handle to the EXT kernels and re-creates the multipliers) or "base" /
+        ALG_SCEN_KERNELS_BASE (a handle with the base constraint set keeps the base kernels -- fused pass, teams, hand-off -- and its
+        multipliers).  Only while the handle carries no per-game data; see alg_set_scenario_kernels."""
+        if isinstance(which, str):
+            if which not in SCEN_KERNELS:
+                raise ValueError(f"scenario_kernels: one of {SCEN_KERNELS}, got {which!r}")
+            which = SCEN_KERNELS.index(which)
+        self.lib.check(self.lib.set_scenario_kernels(self.h, int(which)))
+
+    def get_scenario_kernels(self):
+        """(setting, in_use): the ALG_SCEN_KERNELS_* value and the kernels the next launch takes -- 0 base, 1 EXT, 2 base kernels
+        reading per-game blocks."""
+        w, u = C.c_int32(), C.c_int32()
+        self.lib.check(self.lib.get_scenario_kernels(self.h, C.byref(w), C.byref(u)))
+        return w.value, u.value
 
     # ---- data movement -----------------------------------------------------------------------
     def set_traj(self, z, which=ALG_TRAJ_PD):

@@ -101,7 +101,8 @@ __device__ __forceinline__ T sel_player(const ALG_AS4 T* tab, int i, F&& f) {
     return v;
 }
 // The same selection for a per-player scenario number: the EXT instantiations take it from the game's scenario block (uniform-address
-// loads at constant offsets), the base ones from the kernel-argument table as before.
+// loads at constant offsets), the EXT_ = 2 ones from the same block through the constant address space (the table's code with another base pointer), the base
+// ones from the kernel-argument table as before.
 template <class C, int NP, class F>
 __device__ __forceinline__ double scen_player(CPR pr, const Game& G, const ALG_AS4 double* shared, int off, int i, F&& f) {
     if constexpr (C::EXT) {
@@ -110,6 +111,8 @@ __device__ __forceinline__ double scen_player(CPR pr, const Game& G, const ALG_A
 #pragma unroll
         for (int q = 1; q < NP; q++) v = (i == q) ? tab[f(q)] : v;
         return v;
+    } else if constexpr (C::SCEN) {
+        return sel_player<NP>(G.scen_k(pr) + off, i, f);
     } else {
         return sel_player<NP>(shared, i, f);
     }

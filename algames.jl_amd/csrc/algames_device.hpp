@@ -162,7 +162,10 @@ struct Cfg {
     static constexpr int MODEL = MODEL_, P = P_, D = D_;
     static constexpr bool LS_STAGE = LS_ != 0;
     static constexpr int NW = NW_, NT = NW_ * 64;          // wavefronts / threads per game
-    static constexpr bool EXT = EXT_ != 0;
+    static constexpr bool EXT = EXT_ == 1;
+    // EXT_ = 2: the base constraint set, lane roles and LDS layouts of EXT_ = 0 with the five scenario numbers (pair radii, collision-cost radius /
+    // weight, control bounds) read from the game's scenario block instead of Params (alg_set_scenario_kernels)
+    static constexpr bool SCEN = EXT_ != 0;
     static constexpr bool POS = (P_ > 1) || EXT;     // position blocks (pair / wall / circle terms) present in Q^_i
     // QuadrotorGame (quadrotor.jl:20-46): dense 12 x 12 / 12 x 4 Jacobian blocks per player, n up to 48
     static constexpr bool QUAD = MODEL_ == ALG_MODEL_QUADROTOR;
@@ -177,7 +180,7 @@ struct Cfg {
     static constexpr int NPAIR = P_ * (P_ - 1);
     // position dimensions that carry pair / wall terms: px[i] = (x, y) everywhere (double_integrator.jl:19, unicycle.jl, bicycle.jl);
     // the 3-D ingredients (spherical collision avoidance, Wall3D, Cylinder) act on pz[i][1:3] = (x, y, z) of DoubleIntegrator d = 3
-    static constexpr int PD = (EXT_ != 0 && ((MODEL_ == ALG_MODEL_DOUBLE_INTEGRATOR && D_ == 3) || QUAD)) ? 3 : 2;
+    static constexpr int PD = (EXT_ == 1 && ((MODEL_ == ALG_MODEL_DOUBLE_INTEGRATOR && D_ == 3) || QUAD)) ? 3 : 2;
     static constexpr int NS = PD * (PD + 1) / 2;          // entries of a symmetric PD x PD block: (0,0) (0,1) (1,1) [(0,2) (1,2) (2,2)]
     __host__ __device__ static constexpr int sym(int a, int c) { return PD == 2 ? a + c : (a > c ? a * (a + 1) / 2 + c : c * (c + 1) / 2 + a); }
     // quadrotor: per player [A_i (12 x 12, row-major) | B_i (12 x 4) | RK2(x_k, u_k) entries of the player (12)]
@@ -189,7 +192,7 @@ struct Cfg {
     // (the 3-D EXT instantiation carries 3 x 3 position blocks and does not fit 128 VGPRs without scratch)
     // (the LDS-resident dense direction of the larger configurations leaves room for less than one wavefront per SIMD)
     // (team kernels run small batches -- at most two wavefronts per SIMD are resident -- so they take the 256-register budget as well)
-    static constexpr int WPE = (DENSE && n >= 24) ? 1 : (DENSE || n >= 16 || MODEL_ != ALG_MODEL_DOUBLE_INTEGRATOR || (EXT_ != 0 && D_ == 3) || NW_ > 1) ? 2 : 4;
+    static constexpr int WPE = (DENSE && n >= 24) ? 1 : (DENSE || n >= 16 || MODEL_ != ALG_MODEL_DOUBLE_INTEGRATOR || (EXT_ == 1 && D_ == 3) || NW_ > 1) ? 2 : 4;
     // reuse the accepted line-search trial as the next record! (one assemble pass less per Newton iteration)
     static constexpr bool TRIAL_REUSE = true;
     // forward / costate sweeps of the tile path: time steps whose record slice / gains / dx are in flight (register ring, loop unrolled by it)
@@ -760,11 +763,17 @@ struct Game {
     __device__ __forceinline__ alg_record* hist(CPR pr) const { return as_global(pr.hist) + (size_t)g * pr.hist_max; }
     // this game's scenario block (EXT instantiations; g is wave-uniform, so every read of it is a uniform-address load)
     __device__ __forceinline__ const double* scen(CPR pr) const { return as_global(pr.scen) + (size_t)g * pr.scen_stride; }
+    // the same block for the EXT_ = 2 instantiations: nothing writes it during a launch and g is wave-uniform, so the pointer is stated in the
+    // constant address space, like Params itself: a read compiles to what the base kernel's read of the Params field compiles to -- the call
+    // sites index with the lane's (step, player) item or control, so the number arrives by one vector load with the block pointer as scalar
+    // base where the base kernel has one from the kernel-argument segment
+    __device__ __forceinline__ const ALG_AS4 double* scen_k(CPR pr) const { return (const ALG_AS4 double*)(unsigned long long)pr.scen + (size_t)g * pr.scen_stride; }
 };
 // A scenario number: from the game's block in the EXT instantiations, from the handle's Params in the base ones.  (A macro: the base
 // instantiations keep the very expression `pr.field[idx]` they always had -- a helper taking the field's address compiled to a
 // different instruction schedule of the base kernels.)
-#define ALG_SCEN_AT(C, pr, G, field, off, idx) ((C::EXT) ? (G).scen(pr)[(off) + (idx)] : (pr).field[idx])
+// The EXT_ = 2 instantiations (base set, numbers of the game) read the block through the constant address space.
+#define ALG_SCEN_AT(C, pr, G, field, off, idx) ((C::EXT) ? (G).scen(pr)[(off) + (idx)] : (C::SCEN) ? (G).scen_k(pr)[(off) + (idx)] : (pr).field[idx])
 // the game's extended-constraint table (the `ec` argument of ext_sbmax .. ext_cyls)
 __device__ __forceinline__ const double* scen_ext(CPR pr, const Game& G) { return G.scen(pr) + SC_EXT; }
 __device__ __forceinline__ Game game_view(CPR pr, int g) {

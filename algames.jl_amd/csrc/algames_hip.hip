@@ -11,8 +11,12 @@
 #include <vector>
 
 // every kernel instantiation lives in its own translation unit: the base configurations in algames_base.hip (compiled once per
-// entry), the EXT instantiations in algames_ext_*.hip, the team kernels in algames_mw.hip, the dense-direction ones in theirs
+// entry; algames_base_scen.hip / algames_mw_scen.hip: their twins that read the game's scenario block), the EXT instantiations in
+// algames_ext_*.hip, the team kernels in algames_mw.hip, the dense-direction ones in theirs
 ALG_CFGS_BASE(ALG_DECLARE_KERNELS)
+ALG_CFGS_BASE_SCEN(ALG_DECLARE_KERNELS)
+ALG_CFGS_MW_SCEN(ALG_DECLARE_MW)
+ALG_CFGS_HANDOFF_SCEN(ALG_DECLARE_HO)
 ALG_CFGS_EXT(ALG_DECLARE_KERNELS)
 ALG_CFGS_DENSE(ALG_DECLARE_KERNELS)
 ALG_CFGS_DI1(ALG_DECLARE_KERNELS)
@@ -117,10 +121,13 @@ void recount_con(Params& p) {
     p.con_len = p.col_len + p.ctl_len + p.sb_len + p.wall_len + p.circ_len + p.wall3_len + p.cyl_len;
 }
 
-// supported template instantiations: ALG_CFGS_BASE / ALG_CFGS_EXT (algames_kernels.hpp)
+// supported template instantiations: ALG_CFGS_BASE / ALG_CFGS_EXT (algames_kernels.hpp).  Params::ext: 0 = base kernels, 1 = EXT kernels,
+// 2 = base layout (constraint rows, multipliers: everything recount_con / alloc_con derive is that of 0) with per-game scenario blocks
+// uploaded: the Cfg::SCEN twins of the base kernels (alg_set_scenario_kernels)
 bool cfg_supported(const Params& p, int ext) {
 #define X(M, P, D, E) if (p.model == (M) && p.p == (P) && p.d == (D) && ext == (E)) return true;
     ALG_CFGS_BASE(X)
+    ALG_CFGS_BASE_SCEN(X)
     ALG_CFGS_EXT(X)
     ALG_CFGS_DENSE(X)
     ALG_CFGS_DI1(X)
@@ -162,6 +169,7 @@ struct Handle {
     std::vector<double> scen_games;   // ... host copy (B x scen_stride)
     int scen_stride = 0;          // doubles per block (pad16 of the block length)
     unsigned scen_kinds = 0;      // bit k: kind k holds per-game values
+    int scen_kernels = ALG_SCEN_KERNELS_EXT;   // which instantiations per-game data of the base kinds runs on (alg_set_scenario_kernels)
     int waves_per_game = 0;       // 0 = automatic (alg_set_waves_per_game)
     int handoff = 0;              // straggler hand-off budget (alg_set_handoff; 0 = off)
     int* d_ho = nullptr;          // its queue [count | game indices] (B + 1 ints)
@@ -215,7 +223,7 @@ int launch_check(const char* what) {
             hipLaunchKernelGGL((kernel<decltype(cfg_)>), dim3(grid_), dim3(WAVE), 0, H->stream, __VA_ARGS__); \
             done_ = true;                                                                       \
         };                                                                                      \
-        ALG_CFGS_BASE(LAUNCH_CASE_) ALG_CFGS_EXT(LAUNCH_CASE_) ALG_CFGS_DENSE(LAUNCH_CASE_) ALG_CFGS_DI1(LAUNCH_CASE_) \
+        ALG_CFGS_BASE(LAUNCH_CASE_) ALG_CFGS_BASE_SCEN(LAUNCH_CASE_) ALG_CFGS_EXT(LAUNCH_CASE_) ALG_CFGS_DENSE(LAUNCH_CASE_) ALG_CFGS_DI1(LAUNCH_CASE_) \
         if (!done_) return fail(ALG_ERR_ARG, "unsupported (model, p, d) configuration");        \
         int rc_ = launch_check(#kernel);                                                        \
         if (rc_ != ALG_OK) return rc_;                                                          \
@@ -302,6 +310,7 @@ int team_width(const Handle* hd) {
         if (hd->waves_per_game == (W)) return (W);                                                                    \
         if (hd->waves_per_game == 0 && (long long)p.B * (W) <= 2048 && (W) > best) best = (W); }
     ALG_CFGS_MW(X)
+    ALG_CFGS_MW_SCEN(X)
 #undef X
 #define X(M, P, D, E, W) if (p.model == (M) && p.p == (P) && p.d == (D) && p.ext == (E)) {                         \
         if (hd->waves_per_game == (W)) return (W);                                                                    \
@@ -326,6 +335,7 @@ int launch_newton_solve(Handle* h, int init, uint64_t game_id0) {
         hipLaunchKernelGGL((k_newton_solve_ho<Cfg<M, P, D, E>>), dim3(pr.B), dim3(WAVE), 0, h->stream, h->pr, init, game_id0, h->handoff);  \
         hipLaunchKernelGGL((k_newton_resume<Cfg<M, P, D, E, W, 0>>), dim3(pr.B), dim3(WAVE * (W)), 0, h->stream, h->pr); done = true; }
         ALG_CFGS_HANDOFF(X)
+        ALG_CFGS_HANDOFF_SCEN(X)
 #undef X
         if (done) return launch_check("k_newton_solve_ho / k_newton_resume");
     }
@@ -334,6 +344,7 @@ int launch_newton_solve(Handle* h, int init, uint64_t game_id0) {
 #define X(M, P, D, E, W) if (!done && nw == (W) && pr.model == (M) && pr.p == (P) && pr.d == (D) && pr.ext == (E)) {                   \
         hipLaunchKernelGGL((k_newton_solve<Cfg<M, P, D, E, W>>), dim3(pr.B), dim3(WAVE * (W)), 0, h->stream, h->pr, init, game_id0); done = true; }
     ALG_CFGS_MW(X)
+    ALG_CFGS_MW_SCEN(X)
     ALG_CFGS_MW_DENSE(X)
 #undef X
     return launch_check("k_newton_solve (team)");
@@ -346,6 +357,7 @@ int launch_mpc_loop(Handle* h, int steps, uint64_t game_id0, double* d_states) {
 #define X(M, P, D, E, W) if (!done && nw == (W) && pr.model == (M) && pr.p == (P) && pr.d == (D) && pr.ext == (E)) {                   \
         hipLaunchKernelGGL((k_mpc_loop<Cfg<M, P, D, E, W>>), dim3(pr.B), dim3(WAVE * (W)), 0, h->stream, h->pr, steps, game_id0, d_states); done = true; }
     ALG_CFGS_MW(X)
+    ALG_CFGS_MW_SCEN(X)
     ALG_CFGS_MW_DENSE(X)
 #undef X
     return launch_check("k_mpc_loop (team)");
@@ -517,8 +529,9 @@ int alg_set_handoff(alg_handle* h, int32_t iters) {
         bool have = false;
 #define X(M, P, D, E, W) if (H->pr.model == (M) && H->pr.p == (P) && H->pr.d == (D) && H->pr.ext == (E)) have = true;
         ALG_CFGS_HANDOFF(X)
+        ALG_CFGS_HANDOFF_SCEN(X)
 #undef X
-        if (!have) return fail(ALG_ERR_ARG, "alg_set_handoff: no hand-off kernel pair is compiled for this configuration (3-player DoubleIntegrator d = 2, 3- / 4-player Unicycle, base constraint set)");
+        if (!have) return fail(ALG_ERR_ARG, "alg_set_handoff: no hand-off kernel pair is compiled for this configuration (3-player DoubleIntegrator d = 2, 3- / 4-player Unicycle, base constraint set on the base kernels)");
         if (!H->d_ho) {
             int rc = use_device(H); if (rc) return rc;
             if ((rc = dalloc(H, &H->d_ho, (size_t)H->pr.B + 1, "hand-off queue"))) return rc;
@@ -593,12 +606,14 @@ static void scen_image(const Handle* hd, double* blk) {
     for (size_t e = 0; e < hd->extc.size(); e++) blk[SC_EXT + e] = hd->extc[e];
 }
 // After every adder of an EXT handle: the shared image is uploaded again and any per-game scenario data is dropped (the kernels read
-// the shared image from then on).  Nothing to do for a base handle: its kernels read Params.
+// the shared image from then on).  Nothing to upload for a base handle: its kernels read Params -- one that ran the block-reading twins
+// of the base kernels (ext = 2) runs the base kernels again.
 static int scen_commit(Handle* hd) {
     Params& p = hd->pr;
     hd->scen_kinds = 0;
     p.scen = hd->d_scen; p.scen_stride = 0;
-    if (!p.ext) return ALG_OK;
+    if (p.ext == 2) p.ext = 0;
+    if (p.ext != 1) return ALG_OK;
     int rc = use_device(hd); if (rc) return rc;
     std::vector<double> img((size_t)hd->scen_stride);
     scen_image(hd, img.data());
@@ -869,19 +884,19 @@ static std::vector<int> scen_map(const Handle* hd, int kind) {
         if (p.has_ctl) { for (int c = 0; c < p.m; c++) m.push_back(SC_UMAX + c); for (int c = 0; c < p.m; c++) m.push_back(SC_UMIN + c); }
         break;
     case ALG_SCEN_STATE_BOUND:
-        if (p.ext && p.has_sb) for (int e = 0; e < 2 * p.p * p.n; e++) m.push_back(SC_EXT + e);
+        if (p.ext == 1 && p.has_sb) for (int e = 0; e < 2 * p.p * p.n; e++) m.push_back(SC_EXT + e);
         break;
     case ALG_SCEN_WALL:
-        if (p.ext) for (int w = 0; w < p.nwall; w++) for (int f = 0; f < 6; f++) m.push_back(ew + f * ALG_MAX_WALLS + w);
+        if (p.ext == 1) for (int w = 0; w < p.nwall; w++) for (int f = 0; f < 6; f++) m.push_back(ew + f * ALG_MAX_WALLS + w);
         break;
     case ALG_SCEN_CIRCLE:
-        if (p.ext) for (int c = 0; c < p.ncirc; c++) for (int f = 0; f < 3; f++) m.push_back(ec + f * ALG_MAX_CIRCLES + c);
+        if (p.ext == 1) for (int c = 0; c < p.ncirc; c++) for (int f = 0; f < 3; f++) m.push_back(ec + f * ALG_MAX_CIRCLES + c);
         break;
     case ALG_SCEN_WALL3D:
-        if (p.ext) for (int w = 0; w < p.nwall3; w++) for (int f = 0; f < 12; f++) m.push_back(e3 + 12 * w + f);
+        if (p.ext == 1) for (int w = 0; w < p.nwall3; w++) for (int f = 0; f < 12; f++) m.push_back(e3 + 12 * w + f);
         break;
     case ALG_SCEN_CYLINDER:       // p (3) l r of each entry; the axis (field 3) stays handle-wide
-        if (p.ext) for (int c = 0; c < p.ncyl; c++) for (int f : {0, 1, 2, 4, 5}) m.push_back(ey + 6 * c + f);
+        if (p.ext == 1) for (int c = 0; c < p.ncyl; c++) for (int f : {0, 1, 2, 4, 5}) m.push_back(ey + 6 * c + f);
         break;
     }
     return m;
@@ -922,7 +937,7 @@ int alg_set_scenario_data(alg_handle* h, int32_t kind, const double* data) {
     if (!data) {                  // back to the shared values
         if (!((H->scen_kinds >> kind) & 1u)) return ALG_OK;
         H->scen_kinds &= ~(1u << kind);
-        if (!H->scen_kinds) { p.scen = H->d_scen; p.scen_stride = 0; return ALG_OK; }
+        if (!H->scen_kinds) { p.scen = H->d_scen; p.scen_stride = 0; if (p.ext == 2) p.ext = 0; return ALG_OK; }
         for (int g = 0; g < p.B; g++) for (size_t e = 0; e < L; e++) H->scen_games[g * SS + map[e]] = img[map[e]];
         return h2d(H, H->d_scen_games, H->scen_games.data(), sizeof(double) * SS * p.B);
     }
@@ -952,8 +967,11 @@ int alg_set_scenario_data(alg_handle* h, int32_t kind, const double* data) {
         }
         if (bounds) for (size_t e = 0; e < L / 2; e++) if (!(v[e] >= v[L / 2 + e])) return bad("Upper bounds must be greater than or equal to lower bounds", e);
     }
-    // the first per-game call of a base handle switches it to the EXT instantiation (multipliers re-created like every extended adder)
-    if (!p.ext && (rc = ext_commit(H))) return rc;
+    // the first per-game call of a base handle switches it to the EXT instantiation (multipliers re-created like every extended adder) --
+    // unless the handle was told to stay on the base kernels (alg_set_scenario_kernels): then nothing but the blocks changes, and the
+    // handle runs the twins of the base kernels that read them (ext = 2) while any kind is per game
+    const bool stay_base = p.ext != 1 && H->scen_kernels == ALG_SCEN_KERNELS_BASE;
+    if (!p.ext && !stay_base && (rc = ext_commit(H))) return rc;
     if (!H->scen_kinds) {
         if (!H->d_scen_games && (rc = dalloc(H, &H->d_scen_games, SS * p.B, "scenario blocks (per game)"))) return rc;
         H->scen_games.resize(SS * p.B);
@@ -968,6 +986,23 @@ int alg_set_scenario_data(alg_handle* h, int32_t kind, const double* data) {
     if ((rc = h2d(H, H->d_scen_games, H->scen_games.data(), sizeof(double) * SS * p.B))) return rc;
     H->scen_kinds |= 1u << kind;
     p.scen = H->d_scen_games; p.scen_stride = (int)SS;
+    if (stay_base) p.ext = 2;
+    return ALG_OK;
+}
+int alg_set_scenario_kernels(alg_handle* h, int32_t which) {
+    NEED_HANDLE("alg_set_scenario_kernels");
+    if (which != ALG_SCEN_KERNELS_EXT && which != ALG_SCEN_KERNELS_BASE) return fail(ALG_ERR_ARG, "alg_set_scenario_kernels: ALG_SCEN_KERNELS_EXT (0) or ALG_SCEN_KERNELS_BASE (1)");
+    if (H->scen_kinds) return fail(ALG_ERR_STATE, "alg_set_scenario_kernels: the handle carries per-game scenario data (set every kind back to shared first: alg_set_scenario_data(kind, NULL))");
+    // (a handle that already is EXT -- bicycle, extended constraints -- has no base kernels to stay on: the setting is kept and has no effect)
+    if (which == ALG_SCEN_KERNELS_BASE && H->pr.ext != 1 && !cfg_supported(H->pr, 2))
+        return fail(ALG_ERR_ARG, "alg_set_scenario_kernels: no base kernel that reads per-game scenario blocks is compiled for this configuration (DoubleIntegrator d = 2 p <= 4, d = 3 p = 2; Unicycle p <= 4)");
+    H->scen_kernels = which;
+    return ALG_OK;
+}
+int alg_get_scenario_kernels(alg_handle* h, int32_t* which, int32_t* in_use) {
+    if (!h || !which) return fail(ALG_ERR_ARG, "alg_get_scenario_kernels: null argument");
+    *which = H->scen_kernels;
+    if (in_use) *in_use = H->pr.ext;
     return ALG_OK;
 }
 int alg_get_con_len(alg_handle* h, int32_t* n) {

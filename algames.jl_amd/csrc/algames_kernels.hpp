@@ -1,6 +1,8 @@
 // algames_kernels.hpp -- the __global__ entry points (one workgroup = one wavefront = one game) and the list of compiled
 // (model, p, d, ext) instantiations.  The base instantiations live in algames_hip.hip; the EXT ones (bicycle model, state
 // bounds, walls, circles) are explicitly instantiated in algames_ext_*.hip so that the translation units build in parallel.
+// ext = 2 (Cfg::SCEN without Cfg::EXT): the base kernels with the scenario numbers read from the game's block (algames_base_scen.hip,
+// algames_mw_scen.hip).
 #pragma once
 #include "algames_device.hpp"
 
@@ -259,6 +261,17 @@ __global__ void __launch_bounds__(C::NT, mpc_loop_wpe<C>) k_mpc_loop(Params pr_a
     X(ALG_MODEL_UNICYCLE, 2, 2, 0)                           \
     X(ALG_MODEL_UNICYCLE, 3, 2, 0)                           \
     X(ALG_MODEL_UNICYCLE, 4, 2, 0)
+// The same nine with the scenario numbers taken from the game's block (Cfg::SCEN, ext = 2; alg_set_scenario_kernels): algames_base_scen.hip
+#define ALG_CFGS_BASE_SCEN(X)                               \
+    X(ALG_MODEL_DOUBLE_INTEGRATOR, 1, 2, 2)                  \
+    X(ALG_MODEL_DOUBLE_INTEGRATOR, 2, 2, 2)                  \
+    X(ALG_MODEL_DOUBLE_INTEGRATOR, 3, 2, 2)                  \
+    X(ALG_MODEL_DOUBLE_INTEGRATOR, 4, 2, 2)                  \
+    X(ALG_MODEL_DOUBLE_INTEGRATOR, 2, 3, 2)                  \
+    X(ALG_MODEL_UNICYCLE, 1, 2, 2)                           \
+    X(ALG_MODEL_UNICYCLE, 2, 2, 2)                           \
+    X(ALG_MODEL_UNICYCLE, 3, 2, 2)                           \
+    X(ALG_MODEL_UNICYCLE, 4, 2, 2)
 #define ALG_CFGS_EXT_DI(X)                                  \
     X(ALG_MODEL_DOUBLE_INTEGRATOR, 1, 2, 1)                  \
     X(ALG_MODEL_DOUBLE_INTEGRATOR, 2, 2, 1)                  \
@@ -356,6 +369,12 @@ __global__ void __launch_bounds__(C::NT, mpc_loop_wpe<C>) k_mpc_loop(Params pr_a
     X(ALG_MODEL_UNICYCLE, 3, 2, 0, 4)                        \
     X(ALG_MODEL_UNICYCLE, 4, 2, 0, 2)                        \
     X(ALG_MODEL_UNICYCLE, 4, 2, 0, 4)
+// ... and their twins that read the game's scenario block (algames_mw_scen.hip)
+#define ALG_CFGS_MW_SCEN(X)                                 \
+    X(ALG_MODEL_DOUBLE_INTEGRATOR, 3, 2, 2, 4)               \
+    X(ALG_MODEL_UNICYCLE, 3, 2, 2, 4)                        \
+    X(ALG_MODEL_UNICYCLE, 4, 2, 2, 2)                        \
+    X(ALG_MODEL_UNICYCLE, 4, 2, 2, 4)
 // Team kernels of the dense-direction configurations (algames_mw_dense.hip): where the LDS footprint leaves room for few
 // workgroups per CU at any batch size the automatic choice is the team of four regardless of the batch (team_width, algames_hip.hip)
 #define ALG_CFGS_MW_DENSE(X)                                \
@@ -378,6 +397,10 @@ __global__ void __launch_bounds__(C::NT, mpc_loop_wpe<C>) k_mpc_loop(Params pr_a
     X(ALG_MODEL_DOUBLE_INTEGRATOR, 3, 2, 0, 4)               \
     X(ALG_MODEL_UNICYCLE, 3, 2, 0, 4)                        \
     X(ALG_MODEL_UNICYCLE, 4, 2, 0, 4)
+#define ALG_CFGS_HANDOFF_SCEN(X)                            \
+    X(ALG_MODEL_DOUBLE_INTEGRATOR, 3, 2, 2, 4)               \
+    X(ALG_MODEL_UNICYCLE, 3, 2, 2, 4)                        \
+    X(ALG_MODEL_UNICYCLE, 4, 2, 2, 4)
 #define ALG_INSTANTIATE_HO_PARK(PREFIX, M, P, D, E, W) PREFIX __global__ void k_newton_solve_ho<Cfg<M, P, D, E>>(Params, int, uint64_t, int);
 #define ALG_INSTANTIATE_HO_RESUME(PREFIX, M, P, D, E, W) PREFIX __global__ void k_newton_resume<Cfg<M, P, D, E, W, 0>>(Params);
 #define ALG_DEFINE_HO_RESUME(M, P, D, E, W) ALG_INSTANTIATE_HO_RESUME(template, M, P, D, E, W)

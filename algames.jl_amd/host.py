@@ -666,7 +666,8 @@ def scenario_data(game_cons, game_obj=None, every_kind=False):
     cost may be (B, p).  Checks that every game has game 0's structure (AlgamesError naming the first game and field that differ)
     and returns {ALG_SCEN_* kind: (B, len) array} for the kinds whose numbers differ between the games; kinds equal for all games
     are left out (the handle's shared values, from game 0, hold for them) unless `every_kind` is set.  GameProblem sets it: a
-    problem given per-game data runs on the EXT kernels whatever its games' numbers happen to be, so the arithmetic a game gets does
+    problem given per-game data runs on the kernels that read per-game blocks (EXT, or the base kernels' twins with
+    scenario_kernels="base") whatever its games' numbers happen to be, so the arithmetic a game gets does
     not depend on how a batch is split into shards.  Per-player walls / circles / 3-D walls / cylinders map
     onto game 0's deduplicated table: a game that gives two players different values where game 0 shares one entry is rejected."""
     from ._abi import (ALG_SCEN_COLLISION_RADIUS, ALG_SCEN_COLLISION_COST, ALG_SCEN_CONTROL_BOUND, ALG_SCEN_STATE_BOUND,
@@ -755,7 +756,13 @@ def _obj_row(game_obj, g):
 
 
 class GameProblem:
-    def __init__(self, N, dt, x0, model, opts, game_obj, game_con, backend=None, device=0, game_id0=0):
+    def __init__(self, N, dt, x0, model, opts, game_obj, game_con, backend=None, device=0, game_id0=0, scenario_kernels="ext"):
+        """scenario_kernels: "ext" (default) or "base" -- which kernels per-game data of the base kinds runs on
+        (Batch.set_scenario_kernels).  With "base" a problem that carries only the base constraint set keeps the base kernels (fused
+        pass, teams, hand-off); every base kind the problem carries is still uploaded, so every shard takes the whole batch's path."""
+        if scenario_kernels not in ("ext", "base"):
+            raise ValueError(f"GameProblem: scenario_kernels must be 'ext' or 'base', got {scenario_kernels!r}")
+        self.scenario_kernels = scenario_kernels
         self.probsize = ProblemSize(N, model)
         x0 = np.asarray(x0, dtype=np.float64)
         self.single = x0.ndim == 1
@@ -784,6 +791,8 @@ class GameProblem:
             self.batch.set_bicycle(model.lf, model.lr)
         if isinstance(model, QuadrotorGame) and model.mass != 0.5:
             self.batch.set_quadrotor(model.mass)
+        if scenario_kernels == "base":       # before the adders (the default is not sent: a backend without the entry point keeps working)
+            self.batch.set_scenario_kernels("base")
         self.batch.set_x0(self.x0)
         self.batch.set_lqr(game_obj.Qdiag, game_obj.Rdiag, game_obj.xf, game_obj.uf)
         if game_obj.collision_radius is not None:

@@ -74,16 +74,19 @@ pairs, per-player sets, cylinder axes, the +-inf pattern of the bounds; `setup!`
 differs); they may differ in x0, in the LQR data and in the constraint and collision-cost numbers (radii, bounds, obstacle positions),
 which are uploaded per game (`alg_set_scenario_data`) where they differ.  The handle lives until `close(bp)` or finalisation,
 so repeated solves (warm starts with `opts.dual_reset = false`, MPC loops) reuse the device buffers.
+`scenario_kernels = :base` (default `:ext`): problems that carry only the base constraint set (pair radii, collision cost, control
+bounds) keep the base kernels -- fused pass, team kernels, straggler hand-off -- when their numbers differ per game
+(`alg_set_scenario_kernels`); `scenario_kernels(bp)` reports the setting and the kernels in use.
 """
 mutable struct BatchedGameProblem{P<:GameProblem}
     probs::Vector{P}
     h::Ptr{Cvoid}
     con_len::Int
-    function BatchedGameProblem(probs::Vector{P}; device::Integer=0) where {P<:GameProblem}
+    function BatchedGameProblem(probs::Vector{P}; device::Integer=0, scenario_kernels::Symbol=:ext) where {P<:GameProblem}
         bp = new{P}(probs, C_NULL, 0)
         finalizer(close, bp)                                        # registered first: a failing setup! must not leak the handle
         try
-            setup!(bp, device)
+            setup!(bp, device; scenario_kernels=scenario_kernels)
         catch
             close(bp)
             rethrow()
@@ -103,7 +106,8 @@ end
 sync_options!(bp::BatchedGameProblem) =       # `opts` is shared by reference and read at solve time, like the reference does
     check(ccall((:alg_set_options, LIB), Cint, (Ptr{Cvoid}, Ref{AlgOptions}), bp.h, Ref(abi_options(bp.probs[1].opts))))
 
-function setup!(bp::BatchedGameProblem, device)
+function setup!(bp::BatchedGameProblem, device; scenario_kernels::Symbol = :ext)
+    scenario_kernels in (:ext, :base) || error("setup!: scenario_kernels must be :ext or :base")
     probs = bp.probs; prob = probs[1]; ps = prob.probsize; B = length(probs)
     N, n, m, p = ps.N, ps.n, ps.m, ps.p
     ni, mi = ps.ni[1], ps.mi[1]
@@ -113,6 +117,8 @@ function setup!(bp::BatchedGameProblem, device)
     h = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:alg_create, LIB), Cint, (Ref{AlgDesc}, Ref{Ptr{Cvoid}}), desc, h))
     bp.h = h[]
+    # before the adders (ALG_SCEN_KERNELS_BASE = 1; the default is the handle's own)
+    scenario_kernels == :base && check(ccall((:alg_set_scenario_kernels, LIB), Cint, (Ptr{Cvoid}, Int32), bp.h, 1))
     sync_options!(bp)
     # x0: B x n, game-major (Julia is column-major: build n x B)
     x0 = hcat([Vector(pr.x0) for pr in probs]...)
@@ -273,6 +279,12 @@ function scenario_values(bp::BatchedGameProblem, pr, kind::Integer, len::Integer
     return v
 end
 
+"(setting, in_use) of alg_get_scenario_kernels: `:ext` / `:base`, and the kernels the next launch takes -- 0 base, 1 EXT, 2 base kernels reading per-game blocks"
+function scenario_kernels(bp::BatchedGameProblem)
+    w = Ref{Int32}(0); u = Ref{Int32}(0)
+    check(ccall((:alg_get_scenario_kernels, LIB), Cint, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}), bp.h, w, u))
+    return (w[] == 1 ? :base : :ext), Int(u[])
+end
 # Upload the kinds whose numbers differ between the problems (the handle holds problem 1's values for the others)
 function upload_scenarios!(bp::BatchedGameProblem)
     B = length(bp.probs)
@@ -490,12 +502,12 @@ struct ShardedGameProblem{P<:GameProblem}
     shards::Vector{BatchedGameProblem{P}}
     cuts::Vector{UnitRange{Int}}
 end
-function ShardedGameProblem(probs::Vector{P}; devices=0:0) where {P<:GameProblem}
+function ShardedGameProblem(probs::Vector{P}; devices=0:0, scenario_kernels::Symbol=:ext) where {P<:GameProblem}
     B, W = length(probs), length(devices)
     per = cld(B, W)                                                 # scenarios.shard_range: ceil(B / W) games per shard, last ones shorter
     cuts = [min((r - 1) * per, B)+1:min(r * per, B) for r in 1:W]
     keep = [r for r in 1:W if !isempty(cuts[r])]
-    shards = [BatchedGameProblem(probs[cuts[r]]; device=collect(devices)[r]) for r in keep]
+    shards = [BatchedGameProblem(probs[cuts[r]]; device=collect(devices)[r], scenario_kernels=scenario_kernels) for r in keep]
     # one kernel shape for all shards (the automatic choice depends on a handle's batch size; the shapes differ at rounding level)
     w = Ref{Int32}(0)
     check(ccall((:alg_get_waves_per_game, LIB), Cint, (Ptr{Cvoid}, Ref{Int32}), shards[1].h, w))

@@ -21,7 +21,7 @@ class ShardedGameProblem:
     does not change them).  A per-game LQR block (arrays with a leading batch axis) is split with the batch.  All shards run the
     same kernel shape: `waves_per_game`, default = what the first shard's batch size selects automatically."""
 
-    def __init__(self, N, dt, x0, model, opts, game_obj, game_con, devices=(0,), backend=None, game_id0=0, waves_per_game=None):
+    def __init__(self, N, dt, x0, model, opts, game_obj, game_con, devices=(0,), backend=None, game_id0=0, waves_per_game=None, scenario_kernels="ext"):
         x0 = np.ascontiguousarray(np.asarray(x0, dtype=np.float64).reshape(-1, model.n))
         self.B, self.devices = x0.shape[0], list(devices)
         if not self.devices:
@@ -33,7 +33,7 @@ class ShardedGameProblem:
             if hi <= lo:
                 continue
             self.shards.append(host.GameProblem(N, dt, x0[lo:hi], model, opts, _slice_obj(game_obj, lo, hi), _slice_con(game_con, lo, hi),
-                                                backend=backend, device=dev, game_id0=game_id0 + lo))
+                                                backend=backend, device=dev, game_id0=game_id0 + lo, scenario_kernels=scenario_kernels))
         self.cuts = [c for c in self.cuts if c[1] > c[0]]
         # one kernel shape for all shards: the automatic choice depends on the batch size of a handle (team kernels for small
         # batches), and the shapes differ at rounding level -- a split must not change which arithmetic a game gets

@@ -181,7 +181,8 @@ int  alg_get_line_search_groups(alg_handle* h, int32_t* on);
  * stream finishes the parked games with the team kernel (four wavefronts per game), which continues the same outer / inner loops.
  * Results per game: the iterations before the hand-off are the one-wavefront kernel's, the ones after it the team kernel's (the two
  * agree to rounding: the norms are summed in a different order, see alg_set_waves_per_game).  0 (default) = off.  Only configurations
- * with a team kernel accept K > 0 (3-player DoubleIntegrator d = 2, 3- / 4-player Unicycle, base constraint set; ALG_ERR_ARG
+ * with a team kernel accept K > 0 (3-player DoubleIntegrator d = 2, 3- / 4-player Unicycle, base constraint set -- with per-game scenario
+ * data only in ALG_SCEN_KERNELS_BASE mode, alg_set_scenario_kernels; ALG_ERR_ARG
  * otherwise); the setting is ignored while the handle runs a team kernel itself and by alg_mpc_solve.  alg_get_handoff also returns
  * the number of games the most recent solve handed over (parked_last may be NULL). */
 int  alg_set_handoff(alg_handle* h, int32_t iters);
@@ -286,14 +287,15 @@ int alg_get_con_len(alg_handle* h, int32_t* con_len);
  *   - ALG_ERR_STATE if the kind was not added; ALG_ERR_ARG (nothing changes) if for any game: a value is non-finite where the
  *     handle's is finite, the +-inf pattern of a bound differs from the handle's, u_max < u_min or x_max < x_min, or a radius
  *     is <= 0 on a pair that exists, a circle or a cylinder.
- *   - per-game data runs on the EXT kernel instantiations.  The first call on a handle that is not EXT yet switches it, which
+ *   - per-game data runs on the EXT kernel instantiations unless alg_set_scenario_kernels (below) says otherwise.  The first call on a handle that is not EXT yet switches it, which
  *     re-creates the multipliers like every extended adder (lambda = 0, mu = rho_0); a configuration without an EXT
  *     instantiation (DoubleIntegrator d = 1) gets ALG_ERR_ARG.  Later calls only upload values and leave lambda and mu alone
  *     (an MPC caller may move obstacles between solves and keep the warm start).
  *   - any later adder (alg_add_*) drops ALL per-game data of the handle: the games share the handle's values again.
  *   - every entry point honours it: solves, the EXT team kernels (dense-direction configurations), the step-wise calls, IBR and
  *     alg_mpc_solve.  The tile-path team kernels exist for the base instantiations only, so a tile-path handle with per-game
- *     data runs the one-wavefront EXT kernels (e.g. the three-player double integrator at 64 MPC seeds). */
+ *     data runs the one-wavefront EXT kernels (e.g. the three-player double integrator at 64 MPC seeds) -- in the default mode;
+ *     ALG_SCEN_KERNELS_BASE keeps teams and hand-off. */
 #define ALG_SCEN_COLLISION_RADIUS 0  /* p*p: [i*p+j] = radius of ordered pair (i,j); diagonal and pairs never added are ignored */
 #define ALG_SCEN_COLLISION_COST   1  /* 2p: radius (p) | mu (p)                                                            */
 #define ALG_SCEN_CONTROL_BOUND    2  /* 2m: u_max (m) | u_min (m)                                                          */
@@ -305,6 +307,27 @@ int alg_get_con_len(alg_handle* h, int32_t* con_len);
 int alg_scenario_data_len(alg_handle* h, int32_t kind, int32_t* len);     /* doubles per game; 0 if the kind was not added */
 int alg_set_scenario_data(alg_handle* h, int32_t kind, const double* data /* B x len, or NULL = back to the shared values */);
 int alg_get_scenario_data(alg_handle* h, int32_t kind, double* data /* B x len; the shared values repeated if not per game */);
+/* Which kernels per-game data of the BASE kinds (0 .. 2: pair radii, collision cost, control bounds) runs on.
+ *   ALG_SCEN_KERNELS_EXT (default): as described above -- the first alg_set_scenario_data call switches the handle to the EXT
+ *     instantiations and re-creates lambda and mu.
+ *   ALG_SCEN_KERNELS_BASE: a handle that carries only the base constraint set stays on the base kernels.  alg_set_scenario_data of
+ *     kinds 0 .. 2 validates and uploads as above and touches nothing else: lambda, mu and alg_get_con_len stay as they are, on the
+ *     first call as on later ones.  While any kind is per game the handle runs the twins of its base kernels that read the five
+ *     numbers from the game's block (same constraint set, fused trial pass, LDS layout and register budget per lane), so the
+ *     tile-path team kernels (automatic at B x W <= 2048, alg_set_waves_per_game), the straggler hand-off (a budget set before or
+ *     after the data stays in force, alg_get_handoff reports the parked games), the step-wise calls, IBR and alg_mpc_solve all
+ *     honour the per-game numbers.  With equal numbers in every block the results are bit-identical to the base kernels'.  Once the
+ *     last kind went back to shared (data = NULL), or an adder dropped the per-game data, the handle runs the base kernels again.
+ *     An adder of the extended set switches to EXT exactly as in the default mode (per-game data dropped, multipliers re-created).
+ * The setting can change only while the handle carries no per-game data (ALG_ERR_STATE otherwise; nothing changes).
+ * ALG_SCEN_KERNELS_BASE on a configuration without such kernels (DoubleIntegrator d = 1, the dense-direction configurations: p >= 5,
+ * d = 3 with p != 2, Quadrotor) gets ALG_ERR_ARG and the handle keeps the default; a handle that already is EXT (bicycle, extended
+ * constraints) accepts the call and ignores the setting.  in_use (may be NULL): the kernels the next launch takes -- 0 base,
+ * 1 EXT, 2 base kernels reading per-game blocks. */
+#define ALG_SCEN_KERNELS_EXT  0
+#define ALG_SCEN_KERNELS_BASE 1
+int alg_set_scenario_kernels(alg_handle* h, int32_t which);
+int alg_get_scenario_kernels(alg_handle* h, int32_t* which, int32_t* in_use);
 
 /* set_traj!/get_traj! (primal_dual_traj.jl:46-107) over the batch: B x traj_len.
  * (ALG_TRAJ_TRIAL after a solve: x_1 = x0; the rest is the library's scratch -- the line search accepts a trial by exchanging buffer
