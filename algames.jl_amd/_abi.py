@@ -21,6 +21,7 @@ ALG_ERR_ARG, ALG_ERR_DEVICE, ALG_ERR_STATE = -1, -2, -3
 # which kernels per-game data of the base kinds runs on (alg_set_scenario_kernels)
 ALG_SCEN_KERNELS_EXT, ALG_SCEN_KERNELS_BASE = 0, 1
 SCEN_KERNELS = ("ext", "base")
+ALG_SCHED_LQR_TARGET = 100      # alg_mpc_set_schedule: xf (p, ni) | uf (p, mi) per MPC step and game
 SCEN_KINDS = ("collision_radius", "collision_cost", "control_bound", "state_bound", "wall", "circle", "wall3d", "cylinder")
 
 
@@ -149,10 +150,13 @@ SIGNATURES = {
     "get_scenario_data": (C.c_int, [_P, C.c_int32, _D]),
     "set_scenario_kernels": (C.c_int, [_P, C.c_int32]),
     "get_scenario_kernels": (C.c_int, [_P, _I, _I]),
+    "mpc_set_schedule": (C.c_int, [_P, C.c_int32, C.c_int32, _D]),
+    "mpc_get_schedule": (C.c_int, [_P, C.c_int32, _I]),
 }
 # Entry points a backend may lack (the CPU oracle has no per-game scenario data): bound when present; calling one that is absent
 # raises AlgamesError naming the backend.
-OPTIONAL = frozenset({"scenario_data_len", "set_scenario_data", "get_scenario_data", "set_scenario_kernels", "get_scenario_kernels"})
+OPTIONAL = frozenset({"scenario_data_len", "set_scenario_data", "get_scenario_data", "set_scenario_kernels", "get_scenario_kernels",
+                      "mpc_set_schedule", "mpc_get_schedule"})
 
 
 class AlgamesError(RuntimeError):
@@ -606,6 +610,37 @@ class Batch:
         states = np.empty((steps + 1, self.B, self.n)) if record_states else None
         self.lib.check(self.lib.mpc_solve(self.h, int(steps), int(game_id0), _dptr(states)))
         return states
+
+    # ---- schedules of the fused loop (alg_mpc_set_schedule) ----------------------------------
+    def _sched_kind(self, kind):
+        """(ABI kind, doubles per game and row) of a schedule kind: "lqr_target" / ALG_SCHED_LQR_TARGET or a scenario kind."""
+        if kind == "lqr_target" or (not isinstance(kind, str) and int(kind) == ALG_SCHED_LQR_TARGET):
+            return ALG_SCHED_LQR_TARGET, self.p * self.ni + self.p * self.mi
+        if isinstance(kind, str) and kind not in SCEN_KINDS:
+            raise ValueError(f"unknown schedule kind {kind!r}; 'lqr_target' or one of {SCEN_KINDS}")
+        k = self._kind(kind)
+        return k, self.scenario_data_len(k)
+
+    def mpc_set_schedule(self, kind, data):
+        """Values per MPC step and game of one kind for mpc_solve: data (rows, B, len), step t of the loop takes row min(t, rows - 1);
+        None drops the kind's schedule.  kind: a scenario kind (name in SCEN_KINDS or ALG_SCEN_* value; len = scenario_data_len(kind)) or
+        "lqr_target" (len = p ni + p mi: xf (p, ni) | uf (p, mi) of every game).  See alg_mpc_set_schedule."""
+        k, L = self._sched_kind(kind)
+        if data is None:
+            self.lib.check(self.lib.mpc_set_schedule(self.h, k, 0, None))
+            return
+        a = np.ascontiguousarray(np.asarray(data, dtype=np.float64))
+        if a.ndim != 3 or a.shape[0] < 1 or a.shape[1:] != (self.B, L):
+            raise ValueError(f"schedule of kind {kind!r}: expected shape (rows >= 1, {self.B}, {L}), got {a.shape}")
+        self.lib.check(self.lib.mpc_set_schedule(self.h, k, a.shape[0], _dptr(a)))
+        self._refresh_con_len()
+
+    def mpc_get_schedule(self, kind):
+        """Rows of the kind's schedule, 0 = none."""
+        k, _ = self._sched_kind(kind)
+        v = C.c_int32()
+        self.lib.check(self.lib.mpc_get_schedule(self.h, k, C.byref(v)))
+        return v.value
 
     def mpc_totals(self, reset=False):
         it = np.zeros(self.B, dtype=np.int64); cv = np.zeros(self.B, dtype=np.int64)

@@ -12,7 +12,7 @@
 
 // every kernel instantiation lives in its own translation unit: the base configurations in algames_base.hip (compiled once per
 // entry; algames_base_scen.hip / algames_mw_scen.hip: their twins that read the game's scenario block), the EXT instantiations in
-// algames_ext_*.hip, the team kernels in algames_mw.hip, the dense-direction ones in theirs
+// algames_ext_*.hip, the team kernels in algames_mw.hip, the dense-direction ones in theirs, the scheduled receding-horizon loops in algames_sched.hip
 ALG_CFGS_BASE(ALG_DECLARE_KERNELS)
 ALG_CFGS_BASE_SCEN(ALG_DECLARE_KERNELS)
 ALG_CFGS_MW_SCEN(ALG_DECLARE_MW)
@@ -23,6 +23,15 @@ ALG_CFGS_DI1(ALG_DECLARE_KERNELS)
 ALG_CFGS_MW(ALG_DECLARE_MW)
 ALG_CFGS_MW_DENSE(ALG_DECLARE_MW)
 ALG_CFGS_HANDOFF(ALG_DECLARE_HO)
+// the scheduled receding-horizon loops (algames_sched.hip)
+ALG_CFGS_BASE(ALG_DECLARE_SCHED)
+ALG_CFGS_BASE_SCEN(ALG_DECLARE_SCHED)
+ALG_CFGS_EXT(ALG_DECLARE_SCHED)
+ALG_CFGS_DENSE(ALG_DECLARE_SCHED)
+ALG_CFGS_DI1(ALG_DECLARE_SCHED)
+ALG_CFGS_MW(ALG_DECLARE_SCHED_MW)
+ALG_CFGS_MW_SCEN(ALG_DECLARE_SCHED_MW)
+ALG_CFGS_MW_DENSE(ALG_DECLARE_SCHED_MW)
 
 __global__ void __launch_bounds__(WAVE) k_reset_con(Params pr_arg) {
     CPR pr = kernel_params();
@@ -176,6 +185,15 @@ struct Handle {
     long long records_bound = 0;        // upper bound of the records the Statistics history holds since its last reset (one per record!)
     void* d_scratch = nullptr;    // grow-only scratch of the inspection entry points (dense Jacobians, MPC state logs)
     size_t scratch_bytes = 0;
+    // schedules of alg_mpc_solve (alg_mpc_set_schedule): slot = the ALG_SCEN_* kind, slot 8 = ALG_SCHED_LQR_TARGET; rows = 0: none
+    struct Sched {
+        int rows = 0, len = 0;
+        double* d_data = nullptr;     // rows x B x len, step-major
+        int* d_map = nullptr;         // len block offsets (scen_map; ALG_SCHED_TO_LQR: into the LQR block; < 0: entry skipped)
+        std::vector<double> data;     // host copies: the row the last step used goes into the host mirrors after a loop
+        std::vector<int> map;
+    } sched[ALG_SCHED_MAX_KINDS];
+    bool keep_sched = false;      // set while alg_set_scenario_data's own switch to the EXT kernels runs (it is no adder: schedules stay)
 };
 
 constexpr size_t GUARD = 4096;     // guard zone behind every device buffer (checked by alg_debug_check_guards)
@@ -239,6 +257,18 @@ void dfree(Handle* h, void* q) {
             return;
         }
 }
+
+// schedules of alg_mpc_solve (alg_mpc_set_schedule): dropping one frees its device copies
+void sched_drop(Handle* hd, int slot) {
+    Handle::Sched& sc = hd->sched[slot];
+    if (!sc.rows) return;
+    hipSetDevice(hd->device);
+    hipStreamSynchronize(hd->stream);              // a loop that reads the schedule may still run
+    if (sc.d_data) dfree(hd, sc.d_data);
+    if (sc.d_map) dfree(hd, sc.d_map);
+    sc = Handle::Sched();
+}
+void sched_drop_all(Handle* hd) { for (int k = 0; k < ALG_SCHED_MAX_KINDS; k++) sched_drop(hd, k); }
 
 // strided copies between the dense host layout (B x width) and a per-game segment of an arena (pitch = arena stride)
 int h2d_seg(Handle* h, double* dseg, size_t dpitch_d, const void* src, size_t width_bytes) {
@@ -361,6 +391,27 @@ int launch_mpc_loop(Handle* h, int steps, uint64_t game_id0, double* d_states) {
     ALG_CFGS_MW_DENSE(X)
 #undef X
     return launch_check("k_mpc_loop (team)");
+}
+// ... with the handle's schedules (alg_mpc_set_schedule): the sibling kernels, same shapes
+int launch_mpc_loop_sched(Handle* h, int steps, uint64_t game_id0, double* d_states) {
+    const int nw = team_width(h);
+    if (nw < 0) return fail(ALG_ERR_ARG, "alg_set_waves_per_game: no team kernel of that width is compiled for this configuration");
+    MpcSched sd; std::memset(&sd, 0, sizeof(sd));
+    for (int k = 0; k < ALG_SCHED_MAX_KINDS; k++) {
+        const Handle::Sched& sc = h->sched[k];
+        if (!sc.rows) continue;
+        MpcSchedKind& d = sd.k[sd.nk++];
+        d.data = sc.d_data; d.map = sc.d_map; d.rows = sc.rows; d.len = sc.len;
+    }
+    if (nw == 1) { LAUNCH(k_mpc_loop_sched, h->pr, steps, game_id0, d_states, sd); return ALG_OK; }
+    const Params& pr = h->pr; bool done = false;
+#define X(M, P, D, E, W) if (!done && nw == (W) && pr.model == (M) && pr.p == (P) && pr.d == (D) && pr.ext == (E)) {                   \
+        hipLaunchKernelGGL((k_mpc_loop_sched<Cfg<M, P, D, E, W>>), dim3(pr.B), dim3(WAVE * (W)), 0, h->stream, h->pr, steps, game_id0, d_states, sd); done = true; }
+    ALG_CFGS_MW(X)
+    ALG_CFGS_MW_SCEN(X)
+    ALG_CFGS_MW_DENSE(X)
+#undef X
+    return launch_check("k_mpc_loop_sched (team)");
 }
 
 int alloc_all(Handle* hd) {
@@ -581,6 +632,7 @@ int alg_set_lqr(alg_handle* h, const double* Qd, const double* Rd, const double*
     if ((rc = sync(H))) return rc;
     p.lqr_per_game = per_game ? 1 : 0; p.lqr_stride = per_game ? blk : 0;
     H->lqr_set = true;
+    sched_drop(H, ALG_SCHED_MAX_KINDS - 1);        // the target schedule goes with the data it was set against
     return ALG_OK;
 }
 
@@ -610,6 +662,7 @@ static void scen_image(const Handle* hd, double* blk) {
 // of the base kernels (ext = 2) runs the base kernels again.
 static int scen_commit(Handle* hd) {
     Params& p = hd->pr;
+    if (!hd->keep_sched) sched_drop_all(hd);       // an adder drops every schedule, as it drops per-game data
     hd->scen_kinds = 0;
     p.scen = hd->d_scen; p.scen_stride = 0;
     if (p.ext == 2) p.ext = 0;
@@ -923,30 +976,16 @@ int alg_get_scenario_data(alg_handle* h, int32_t kind, double* data) {
     }
     return ALG_OK;
 }
-int alg_set_scenario_data(alg_handle* h, int32_t kind, const double* data) {
-    static const char* who = "alg_set_scenario_data";
-    if (!h) return fail(ALG_ERR_ARG, "alg_set_scenario_data: null handle");
-    if (!scen_kind_ok(kind)) return fail(ALG_ERR_ARG, "alg_set_scenario_data: unknown kind");
-    Params& p = H->pr;
-    const std::vector<int> map = scen_map(H, kind);
-    if (map.empty()) return fail(ALG_ERR_STATE, "alg_set_scenario_data: this kind of constraint / cost was not added to the handle");
-    const size_t L = map.size(), SS = (size_t)H->scen_stride;
-    std::vector<double> img(SS);
-    scen_image(H, img.data());
-    int rc = use_device(H); if (rc) return rc;
-    if (!data) {                  // back to the shared values
-        if (!((H->scen_kinds >> kind) & 1u)) return ALG_OK;
-        H->scen_kinds &= ~(1u << kind);
-        if (!H->scen_kinds) { p.scen = H->d_scen; p.scen_stride = 0; if (p.ext == 2) p.ext = 0; return ALG_OK; }
-        for (int g = 0; g < p.B; g++) for (size_t e = 0; e < L; e++) H->scen_games[g * SS + map[e]] = img[map[e]];
-        return h2d(H, H->d_scen_games, H->scen_games.data(), sizeof(double) * SS * p.B);
-    }
-    // validation of every game before anything changes
+// The rules every game's values of one kind must meet (alg_set_scenario_data; every row of alg_mpc_set_schedule): `data` = B x L values in the
+// order of `map`, `img` = the handle's shared image.  row >= 0 names the schedule row in the message.
+static int scen_validate(const Handle* hd, const char* who, int kind, const std::vector<int>& map, const std::vector<double>& img, const double* data, int row) {
+    const Params& p = hd->pr;
+    const size_t L = map.size();
     const bool bounds = kind == ALG_SCEN_CONTROL_BOUND || kind == ALG_SCEN_STATE_BOUND;
     for (int g = 0; g < p.B; g++) {
         const double* v = data + (size_t)g * L;
         auto bad = [&](const std::string& what, size_t e) {
-            return fail(ALG_ERR_ARG, std::string(who) + ": game " + std::to_string(g) + ", entry " + std::to_string(e) + ": " + what);
+            return fail(ALG_ERR_ARG, std::string(who) + ": " + (row >= 0 ? "row " + std::to_string(row) + ", " : std::string()) + "game " + std::to_string(g) + ", entry " + std::to_string(e) + ": " + what);
         };
         for (size_t e = 0; e < L; e++) {
             const double s0 = img[map[e]];
@@ -967,11 +1006,34 @@ int alg_set_scenario_data(alg_handle* h, int32_t kind, const double* data) {
         }
         if (bounds) for (size_t e = 0; e < L / 2; e++) if (!(v[e] >= v[L / 2 + e])) return bad("Upper bounds must be greater than or equal to lower bounds", e);
     }
+    return ALG_OK;
+}
+// alg_set_scenario_data without the bookkeeping of schedules (alg_mpc_set_schedule makes a kind per-game through it, with row 0)
+static int set_scenario_data(alg_handle* h, const char* who, int32_t kind, const double* data, bool validate) {
+    Params& p = H->pr;
+    const std::vector<int> map = scen_map(H, kind);
+    if (map.empty()) return fail(ALG_ERR_STATE, std::string(who) + ": this kind of constraint / cost was not added to the handle");
+    const size_t L = map.size(), SS = (size_t)H->scen_stride;
+    std::vector<double> img(SS);
+    scen_image(H, img.data());
+    int rc = use_device(H); if (rc) return rc;
+    if (!data) {                  // back to the shared values
+        if (!((H->scen_kinds >> kind) & 1u)) return ALG_OK;
+        H->scen_kinds &= ~(1u << kind);
+        if (!H->scen_kinds) { p.scen = H->d_scen; p.scen_stride = 0; if (p.ext == 2) p.ext = 0; return ALG_OK; }
+        for (int g = 0; g < p.B; g++) for (size_t e = 0; e < L; e++) H->scen_games[g * SS + map[e]] = img[map[e]];
+        return h2d(H, H->d_scen_games, H->scen_games.data(), sizeof(double) * SS * p.B);
+    }
+    // validation of every game before anything changes
+    if (validate && (rc = scen_validate(H, who, kind, map, img, data, -1))) return rc;
     // the first per-game call of a base handle switches it to the EXT instantiation (multipliers re-created like every extended adder) --
     // unless the handle was told to stay on the base kernels (alg_set_scenario_kernels): then nothing but the blocks changes, and the
     // handle runs the twins of the base kernels that read them (ext = 2) while any kind is per game
     const bool stay_base = p.ext != 1 && H->scen_kernels == ALG_SCEN_KERNELS_BASE;
-    if (!p.ext && !stay_base && (rc = ext_commit(H))) return rc;
+    if (!p.ext && !stay_base) {
+        H->keep_sched = true; rc = ext_commit(H); H->keep_sched = false;
+        if (rc) return rc;
+    }
     if (!H->scen_kinds) {
         if (!H->d_scen_games && (rc = dalloc(H, &H->d_scen_games, SS * p.B, "scenario blocks (per game)"))) return rc;
         H->scen_games.resize(SS * p.B);
@@ -987,6 +1049,13 @@ int alg_set_scenario_data(alg_handle* h, int32_t kind, const double* data) {
     H->scen_kinds |= 1u << kind;
     p.scen = H->d_scen_games; p.scen_stride = (int)SS;
     if (stay_base) p.ext = 2;
+    return ALG_OK;
+}
+int alg_set_scenario_data(alg_handle* h, int32_t kind, const double* data) {
+    if (!h) return fail(ALG_ERR_ARG, "alg_set_scenario_data: null handle");
+    if (!scen_kind_ok(kind)) return fail(ALG_ERR_ARG, "alg_set_scenario_data: unknown kind");
+    int rc = set_scenario_data(h, "alg_set_scenario_data", kind, data, true); if (rc) return rc;
+    sched_drop(H, kind);          // the caller's values replace what a schedule of this kind would apply
     return ALG_OK;
 }
 int alg_set_scenario_kernels(alg_handle* h, int32_t which) {
@@ -1278,8 +1347,81 @@ int alg_mpc_solve(alg_handle* h, int32_t steps, int64_t game_id0, double* states
     const Params& p = H->pr;
     const size_t cnt = (size_t)(steps + 1) * p.B * p.n;
     if (states && (rc = ensure_scratch(H, sizeof(double) * cnt))) return rc;
-    if ((rc = launch_mpc_loop(H, (int)steps, (uint64_t)game_id0, states ? (double*)H->d_scratch : (double*)nullptr))) return rc;
+    bool scheduled = false;
+    for (int k = 0; k < ALG_SCHED_MAX_KINDS; k++) scheduled |= H->sched[k].rows > 0;
+    if (!scheduled) rc = launch_mpc_loop(H, (int)steps, (uint64_t)game_id0, states ? (double*)H->d_scratch : (double*)nullptr);
+    else rc = launch_mpc_loop_sched(H, (int)steps, (uint64_t)game_id0, states ? (double*)H->d_scratch : (double*)nullptr);
+    if (rc) return rc;
+    // the loop leaves the row its last step used in the games' blocks: the host mirror of the scenario blocks follows (what the step-wise
+    // alg_set_scenario_data calls would have left; the LQR blocks have no host mirror)
+    for (int k = 0; scheduled && k < ALG_SCHED_MAX_KINDS - 1; k++) {
+        const Handle::Sched& sc = H->sched[k];
+        if (!sc.rows) continue;
+        const size_t row = (size_t)std::min((int)steps - 1, sc.rows - 1), SS = (size_t)H->scen_stride;
+        for (int g = 0; g < p.B; g++)
+            for (int e = 0; e < sc.len; e++)
+                if (sc.map[e] >= 0) H->scen_games[g * SS + sc.map[e]] = sc.data[(row * p.B + g) * sc.len + e];
+    }
     if (states) return d2h(H, states, H->d_scratch, sizeof(double) * cnt);
+    return ALG_OK;
+}
+// Schedules of alg_mpc_solve: per game and per MPC step values of one kind (include/algames_hip.h)
+int alg_mpc_set_schedule(alg_handle* h, int32_t kind, int32_t rows, const double* data) {
+    static const char* who = "alg_mpc_set_schedule";
+    NEED_HANDLE("alg_mpc_set_schedule");
+    const bool target = kind == ALG_SCHED_LQR_TARGET;
+    if (!target && !scen_kind_ok(kind)) return fail(ALG_ERR_ARG, "alg_mpc_set_schedule: unknown kind (an ALG_SCEN_* value or ALG_SCHED_LQR_TARGET)");
+    const int slot = target ? ALG_SCHED_MAX_KINDS - 1 : (int)kind;
+    int rc = use_device(H); if (rc) return rc;
+    if (!data) { sched_drop(H, slot); return ALG_OK; }
+    if (rows < 1) return fail(ALG_ERR_ARG, "alg_mpc_set_schedule: rows must be >= 1");
+    const Params& p = H->pr;
+    std::vector<int> map;
+    if (target) {
+        if (!H->lqr_set || !p.lqr_per_game) return fail(ALG_ERR_STATE, "alg_mpc_set_schedule: a target schedule needs per-game LQR data (alg_set_lqr with per_game = 1)");
+        const int wq = p.p * p.ni, wr = p.p * p.mi;      // LQR block: [Qd | xf | Rd | uf]
+        for (int e = 0; e < wq; e++) map.push_back((wq + e) | ALG_SCHED_TO_LQR);
+        for (int e = 0; e < wr; e++) map.push_back((2 * wq + wr + e) | ALG_SCHED_TO_LQR);
+        const size_t cnt = (size_t)rows * p.B * map.size();
+        for (size_t e = 0; e < cnt; e++)
+            if (!std::isfinite(data[e])) return fail(ALG_ERR_ARG, std::string(who) + ": row " + std::to_string(e / ((size_t)p.B * map.size())) + ": targets must be finite");
+    } else {
+        map = scen_map(H, kind);
+        if (map.empty()) return fail(ALG_ERR_STATE, "alg_mpc_set_schedule: this kind of constraint / cost was not added to the handle");
+        // the block-reading twins of the base kernels read their block through the constant address space (scalar loads): it must not change
+        // during a kernel
+        if (kind <= ALG_SCEN_CONTROL_BOUND && p.ext != 1 && H->scen_kernels == ALG_SCEN_KERNELS_BASE)
+            return fail(ALG_ERR_ARG, "alg_mpc_set_schedule: a base kind (collision radius, collision cost, control bound) cannot be scheduled in ALG_SCEN_KERNELS_BASE mode; use the default mode (ALG_SCEN_KERNELS_EXT)");
+        std::vector<double> img((size_t)H->scen_stride);
+        scen_image(H, img.data());
+        for (int r = 0; r < rows; r++)
+            if ((rc = scen_validate(H, who, kind, map, img, data + (size_t)r * p.B * map.size(), r))) return rc;
+        if (p.ext != 1 && H->scen_kernels != ALG_SCEN_KERNELS_BASE && !cfg_supported(p, 1))
+            return fail(ALG_ERR_ARG, "alg_mpc_set_schedule: (model, p, d) has no compiled EXT kernel instantiation to run per-game data on");
+        if (kind == ALG_SCEN_COLLISION_RADIUS)             // diagonal / pairs never added: ignored, as alg_set_scenario_data ignores them
+            for (size_t e = 0; e < map.size(); e++) { const int i = (int)e / p.p, j = (int)e % p.p; if (i == j || !((p.ca_mask[i] >> j) & 1u)) map[e] = -1; }
+    }
+    // the device copies first: a failure here leaves the handle as it was
+    Handle::Sched sc;
+    sc.rows = rows; sc.len = (int)map.size();
+    const size_t cnt = (size_t)rows * p.B * map.size();
+    if ((rc = dalloc(H, &sc.d_data, cnt, "schedule rows"))) return rc;
+    if ((rc = dalloc(H, &sc.d_map, map.size(), "schedule block offsets")) || (rc = h2d(H, sc.d_data, data, sizeof(double) * cnt)) ||
+        (rc = h2d(H, sc.d_map, map.data(), sizeof(int) * map.size()))) {
+        dfree(H, sc.d_data); if (sc.d_map) dfree(H, sc.d_map);
+        return rc;
+    }
+    // a scenario kind becomes per game exactly as alg_set_scenario_data(kind, row 0) makes it
+    if (!target && (rc = set_scenario_data(h, who, kind, data, false))) { dfree(H, sc.d_data); dfree(H, sc.d_map); return rc; }
+    sc.data.assign(data, data + cnt); sc.map = map;
+    sched_drop(H, slot);
+    H->sched[slot] = std::move(sc);
+    return ALG_OK;
+}
+int alg_mpc_get_schedule(alg_handle* h, int32_t kind, int32_t* rows) {
+    if (!h || !rows) return fail(ALG_ERR_ARG, "alg_mpc_get_schedule: null argument");
+    if (kind != ALG_SCHED_LQR_TARGET && !scen_kind_ok(kind)) return fail(ALG_ERR_ARG, "alg_mpc_get_schedule: unknown kind (an ALG_SCEN_* value or ALG_SCHED_LQR_TARGET)");
+    *rows = H->sched[kind == ALG_SCHED_LQR_TARGET ? ALG_SCHED_MAX_KINDS - 1 : (int)kind].rows;
     return ALG_OK;
 }
 int alg_mpc_totals(alg_handle* h, int64_t* it, int64_t* cv, int32_t reset) {

@@ -248,6 +248,74 @@ __global__ void __launch_bounds__(C::NT, mpc_loop_wpe<C>) k_mpc_loop(Params pr_a
     }
 }
 
+// The receding-horizon loop with a SCHEDULE (alg_mpc_set_schedule): per game and per MPC step values of the numbers that may differ per
+// game -- the kinds of the scenario block and the LQR targets xf / uf.  A sibling of k_mpc_loop, not one more argument of it: k_mpc_loop's
+// source, and with it the binary of every unscheduled loop, stays what it was; the siblings live in translation units of
+// their own (algames_sched.hip) and are launched only while the handle carries a schedule.
+// The schedule sits in device memory in compact form, rows x B x len doubles per kind, with a table of len block offsets per kind (the host's
+// scen_map; ALG_SCHED_TO_LQR marks an offset into the game's LQR block, a negative entry is skipped like alg_set_scenario_data skips it).
+// Before every solve the game's wavefronts copy row min(t, rows - 1) of every kind into the game's own blocks with ordinary vector stores.
+// The solver reads those blocks with vector loads (as_global), through the CU's vector L1 the stores went through, behind a workgroup
+// barrier.  The ALG_AS4 readers of the block (Cfg::SCEN without Cfg::EXT: constant address space, memory the compiler takes as unchanged
+// during a kernel) must not meet a scheduled scenario kind: the host refuses that (alg_mpc_set_schedule).
+constexpr int ALG_SCHED_MAX_KINDS = 9;                 // the eight ALG_SCEN_* kinds + ALG_SCHED_LQR_TARGET
+constexpr int ALG_SCHED_TO_LQR = 1 << 30;
+struct MpcSchedKind { const double* data; const int* map; int rows, len; };
+struct MpcSched { int nk, pad_; MpcSchedKind k[ALG_SCHED_MAX_KINDS]; };
+struct MpcLoopSchedArgs { Params pr; int steps; uint64_t game_id0; double* states; MpcSched sd; };
+template <class C>
+__device__ __forceinline__ void mpc_apply_schedule(CPR pr, const ALG_AS4 MpcSched& sd, const int g, const int t) {
+    const int tid = phase_lane(), nk = sd.nk;
+    double* const scen = as_global(const_cast<double*>(pr.scen)) + (size_t)g * pr.scen_stride;
+    double* const lqr = as_global(const_cast<double*>(pr.lqr)) + (size_t)g * pr.lqr_stride;
+    for (int k = 0; k < nk; k++) {
+        const int len = sd.k[k].len, rows = sd.k[k].rows, row = t < rows ? t : rows - 1;      // the last row is held
+        const double* const src = as_global(sd.k[k].data) + ((size_t)row * pr.B + g) * len;
+        const int* const map = as_global(sd.k[k].map);
+        for (int e = tid; e < len; e += C::NT) {
+            const int o = map[e];
+            if (o < 0) continue;
+            if (o & ALG_SCHED_TO_LQR) lqr[o & ~ALG_SCHED_TO_LQR] = src[e];
+            else scen[o] = src[e];
+        }
+    }
+}
+template <class C>
+__global__ void __launch_bounds__(C::NT, mpc_loop_wpe<C>) k_mpc_loop_sched(Params pr_arg, int steps_arg, uint64_t game_id0_arg, double* states_arg, MpcSched sd_arg) {
+    __shared__ Lds<C> L;
+    CPR pr = kernel_params();
+#if defined(__HIP_DEVICE_COMPILE__)
+    const ALG_AS4 MpcLoopSchedArgs& ka = *(const ALG_AS4 MpcLoopSchedArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+#else
+    const MpcLoopSchedArgs& ka = *(const MpcLoopSchedArgs*)nullptr;      // host pass: never executed
+#endif
+    const int g = blockIdx.x;
+    Game G = game_view(pr, g);
+    auto kq = [&]() -> const ALG_AS4 MpcLoopSchedArgs& { return *(const ALG_AS4 MpcLoopSchedArgs*)uniform_u64((unsigned long long)&ka); };
+    {
+        double* const st0 = kq().states; const int l0 = phase_lane();
+        if (st0 && l0 < C::n) { const Game H = G.fresh(); CPR pr0 = phase_params(pr); st0[(size_t)phase_int(g) * C::n + l0] = H.x0(pr0)[l0]; }
+    }
+    if (kq().steps < 1) return;
+    for (int t = 0; ; t++) {
+        // the schedule phase: between the advance of step t - 1 and the solve of step t (and before step 0), bracketed by barriers, everything
+        // of it re-derived from the opaque roots -- nothing of it lives across the solve
+        __syncthreads();
+        mpc_apply_schedule<C>(phase_params(pr), kq().sd, phase_int(g), t);
+        __syncthreads();
+        const int gq = phase_int(g);
+        newton_solve<C, 0, mpc_loop_launder_v<C>>(pr, G, L, 1, kq().game_id0 + (uint64_t)t * 1000003ull + (uint64_t)gq, t == 0 ? -1 : 1, t == 0 ? -1 : 0);
+        __syncthreads();
+        mpc_advance<C>(phase_params(pr), G.fresh());
+        __syncthreads();
+        double* const states = kq().states;
+        const int ln = phase_lane();
+        if (states && ln < C::n) { CPR prs = phase_params(pr); states[((size_t)(t + 1) * prs.B + phase_int(g)) * C::n + ln] = G.fresh().z(0)[ln]; }
+        __syncthreads();
+        if (t + 1 >= kq().steps) break;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Instantiation lists: X(model, p, d, ext)
 // ------------------------------------------------------------------------------------------------
@@ -409,3 +477,10 @@ __global__ void __launch_bounds__(C::NT, mpc_loop_wpe<C>) k_mpc_loop(Params pr_a
 #define ALG_DECLARE_MW(M, P, D, E, W) ALG_INSTANTIATE_MW(extern template, M, P, D, E, W)
 #define ALG_DEFINE_KERNELS(M, P, D, E) ALG_INSTANTIATE_KERNELS(template, M, P, D, E)
 #define ALG_DECLARE_KERNELS(M, P, D, E) ALG_INSTANTIATE_KERNELS(extern template, M, P, D, E)
+// The scheduled receding-horizon loops (k_mpc_loop_sched): one per loop kernel of the lists above, defined in algames_sched.hip
+#define ALG_INSTANTIATE_SCHED(PREFIX, M, P, D, E) PREFIX __global__ void k_mpc_loop_sched<Cfg<M, P, D, E>>(Params, int, uint64_t, double*, MpcSched);
+#define ALG_INSTANTIATE_SCHED_MW(PREFIX, M, P, D, E, W) PREFIX __global__ void k_mpc_loop_sched<Cfg<M, P, D, E, W>>(Params, int, uint64_t, double*, MpcSched);
+#define ALG_DEFINE_SCHED(M, P, D, E) ALG_INSTANTIATE_SCHED(template, M, P, D, E)
+#define ALG_DECLARE_SCHED(M, P, D, E) ALG_INSTANTIATE_SCHED(extern template, M, P, D, E)
+#define ALG_DEFINE_SCHED_MW(M, P, D, E, W) ALG_INSTANTIATE_SCHED_MW(template, M, P, D, E, W)
+#define ALG_DECLARE_SCHED_MW(M, P, D, E, W) ALG_INSTANTIATE_SCHED_MW(extern template, M, P, D, E, W)

@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import (ALG_MODEL_BICYCLE, ALG_MODEL_DOUBLE_INTEGRATOR, ALG_MODEL_QUADROTOR, ALG_MODEL_UNICYCLE, ALG_TRAJ_PD, ALG_TRAJ_TRIAL,
-                   ALG_TRAJ_DELTA, AlgamesError, Batch, CLib)
+                   ALG_TRAJ_DELTA, ALG_SCHED_LQR_TARGET, AlgamesError, Batch, CLib)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.environ.get("ALGAMES_HIP_LIB", os.path.join(_HERE, "lib", "libalgames_hip.so"))
@@ -1033,25 +1033,60 @@ def ibr_newton_solve(prob, i=None, ibr_opts=None, init=True):
 # `opts.shift` / `opts.dual_reset` (options.jl:16-17, primal_dual_traj.jl:35-39, solver_methods.jl:25).  Builder-defined
 # (SURVEY.md 8(d) C5): solve; x0 <- RK2(x_1, u_1); next solve warm-started with shift = 1 and dual_reset = false.
 # --------------------------------------------------------------------------------------------------
-def mpc_solve(prob, steps, record_states=False, fused=True):
+def mpc_solve(prob, steps, record_states=False, fused=True, schedule=None):
     """Runs `steps` receding-horizon solves for every game of the batch.  Returns (newton_iters (B,), converged (B,),
     states (steps+1, B, n) or None).  fused=True: one launch, every game runs its own loop (alg_mpc_solve); fused=False:
     one newton_solve! launch + one advance launch per MPC step (the batch waits for its slowest game at every step).
-    No host synchronisation happens inside the loop unless record_states is set."""
+    No host synchronisation happens inside the loop unless record_states is set.
+
+    schedule: {kind: array (rows, B, len)} -- values per MPC step and game of the numbers that may differ per game; kind is a scenario
+    kind (Batch.set_scenario_data) or "lqr_target" (xf (p, ni) | uf (p, mi) of every game; the problem needs per-game LQR data).  Step t
+    solves with row min(t, rows - 1) of every kind.  fused=True uploads the schedule (Batch.mpc_set_schedule), launches once and drops it
+    again; fused=False applies the step's rows through set_scenario_data / set_lqr before each step's solve -- the definition the fused
+    path is held to.  Either way the handle keeps the rows the last step used."""
     b = prob.batch
+    sched = []
+    for kind in (schedule or {}):
+        k, L = b._sched_kind(kind)
+        a = np.ascontiguousarray(np.asarray(schedule[kind], dtype=np.float64))
+        if a.ndim != 3 or a.shape[0] < 1 or a.shape[1:] != (b.B, L):
+            raise ValueError(f"schedule of kind {kind!r}: expected shape (rows >= 1, {b.B}, {L}), got {a.shape}")
+        sched.append((k, a))
+    sched.sort(key=lambda ka: ka[0])
     b.mpc_totals(reset=True)
     prob._sync_options()
     if fused:
-        states = b.mpc_solve(steps, prob.game_id0, record_states)
-        it, cv = b.mpc_totals()
+        for k, a in sched:
+            b.mpc_set_schedule(k, a)
+        try:
+            states = b.mpc_solve(steps, prob.game_id0, record_states)
+            it, cv = b.mpc_totals()
+        finally:
+            for k, a in sched:
+                b.mpc_set_schedule(k, None)
         return it, cv, states
     shift0, reset0 = prob.opts.shift, prob.opts.dual_reset
     states = [b.get_x0()] if record_states else None
+
+    def apply_rows(t):
+        for k, a in sched:
+            r = min(t, a.shape[0] - 1)
+            if t > 0 and r == min(t - 1, a.shape[0] - 1):
+                continue                            # the last row is held: nothing to upload
+            if k == ALG_SCHED_LQR_TARGET:
+                obj = prob.game_obj
+                if np.ndim(obj.Qdiag) != 3:
+                    raise AlgamesError("mpc_solve: a target schedule needs per-game LQR data (Qdiag, Rdiag of shape (B, p, .))")
+                w = b.p * b.ni
+                b.set_lqr(obj.Qdiag, obj.Rdiag, a[r][:, :w].reshape(b.B, b.p, b.ni), a[r][:, w:].reshape(b.B, b.p, b.mi))
+            else:
+                b.set_scenario_data(k, a[r])
     try:
         for t in range(steps):
             if t == 1:
                 prob.opts.shift, prob.opts.dual_reset = 1, False
                 prob._sync_options()
+            apply_rows(t)
             b.newton_solve_async(init=True, game_id0=prob.game_id0 + t * 1000003)
             b.mpc_advance()
             if record_states:

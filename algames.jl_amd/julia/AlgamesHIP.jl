@@ -8,7 +8,7 @@
 #   bp = BatchedGameProblem(probs; device=0)          one device handle for a batch of structurally identical problems
 #   newton_solve!(bp)                                 src/problem/solver_methods.jl:5-65 for every problem of the batch
 #   ibr_newton_solve!(bp; ibr_opts), ibr_newton_solve!(bp, i)     solver_methods.jl:133-228
-#   mpc_solve!(bp, steps)                             receding-horizon loop of BASELINE config 5 (opts.shift / opts.dual_reset)
+#   mpc_solve!(bp, steps; schedule)                   receding-horizon loop of BASELINE config 5 (opts.shift / opts.dual_reset), with per-step values of targets / obstacles
 #   newton_solve!(probs::Vector{<:GameProblem})       convenience: build a handle, solve, release
 #   sp = ShardedGameProblem(probs; devices=0:7); newton_solve!(sp)     the batch split over several devices (one handle each)
 # After a solve every `prob.pdtraj`, the multipliers / penalties / values of every constraint (`conval.λ`, `.μ`, `.vals`,
@@ -552,20 +552,50 @@ function ibr_newton_solve!(bp::BatchedGameProblem, i::Int)
     return pull_results!(bp, stats)
 end
 
+const SCHED_LQR_TARGET = 100       # ALG_SCHED_LQR_TARGET: xf (p x ni) | uf (p x mi) of every game and MPC step
+"ABI kind of a schedule key: an ALG_SCEN_* value (0 .. 7) or `:lqr_target`"
+sched_kind(k::Integer) = Int32(k)
+sched_kind(k::Symbol) = k == :lqr_target ? Int32(SCHED_LQR_TARGET) : error("mpc_solve!: unknown schedule kind $k (:lqr_target or an ALG_SCEN_* value)")
+"rows of the kind's schedule on the handle, 0 = none (alg_mpc_get_schedule)"
+function mpc_schedule_rows(bp::BatchedGameProblem, kind)
+    rows = Ref{Int32}(0)
+    check(ccall((:alg_mpc_get_schedule, LIB), Cint, (Ptr{Cvoid}, Int32, Ref{Int32}), bp.h, sched_kind(kind), rows))
+    return Int(rows[])
+end
+
 """
-    mpc_solve!(bp, steps; game_id0=0) -> (newton_iters, converged, states)
+    mpc_solve!(bp, steps; game_id0=0, schedule=nothing) -> (newton_iters, converged, states)
 
 Receding-horizon loop of BASELINE config 5, one launch: `steps` x (newton_solve! from the shifted warm start, x0 <- RK2(x_1, u_1)),
 first solve with the handle's shift / dual_reset, later ones with shift = 1 and dual_reset = false (the reference's hooks,
 options.jl:16-17, primal_dual_traj.jl:29-44, solver_methods.jl:25).  `states` is n x B x (steps + 1).
+
+`schedule`: a `Dict` kind => `len x B x rows` array (column-major: the ABI's rows x B x len, step-major) of values per MPC step and game --
+kind an ALG_SCEN_* value or `:lqr_target` (xf | uf of every game; needs per-game LQR data).  The step-th solve (1-based) takes slice min(step, rows) of every
+kind; the schedule is uploaded (`alg_mpc_set_schedule`), applied inside the single launch and dropped again, the handle keeps the rows
+the last step used.
 """
-function mpc_solve!(bp::BatchedGameProblem, steps::Integer; game_id0::Integer=0)
+function mpc_solve!(bp::BatchedGameProblem, steps::Integer; game_id0::Integer=0, schedule=nothing)
     sync_options!(bp)
     B = length(bp.probs); n = bp.probs[1].probsize.n
     iters = zeros(Int64, B); conv = zeros(Int64, B)
     check(ccall((:alg_mpc_totals, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Int32), bp.h, iters, conv, 1))      # reset the totals
     states = zeros(n, B, steps + 1)
-    check(ccall((:alg_mpc_solve, LIB), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}), bp.h, steps, game_id0, states))
+    kinds = schedule === nothing ? Int32[] : sort!([sched_kind(k) for k in keys(schedule)])
+    if schedule !== nothing
+        for (k, V) in schedule
+            A = Array{Float64, 3}(V)
+            size(A, 2) == B && size(A, 3) >= 1 || error("mpc_solve!: schedule of kind $k must be len x $B x rows")
+            check(ccall((:alg_mpc_set_schedule, LIB), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}), bp.h, sched_kind(k), size(A, 3), A))
+        end
+    end
+    try
+        check(ccall((:alg_mpc_solve, LIB), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}), bp.h, steps, game_id0, states))
+    finally
+        for k in kinds
+            check(ccall((:alg_mpc_set_schedule, LIB), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}), bp.h, k, 0, C_NULL))
+        end
+    end
     check(ccall((:alg_mpc_totals, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Int32), bp.h, iters, conv, 0))
     stats = Vector{AlgGameStats}(undef, B)
     check(ccall((:alg_get_stats, LIB), Cint, (Ptr{Cvoid}, Ptr{AlgGameStats}), bp.h, stats))

@@ -146,6 +146,47 @@ def quadrotor_crossing(ids, N=20, seed=100, p=2):
     return model, N, dt, x0, game_obj, game_con, opts
 
 
+GOAL_SPEED = 0.04     # of the moving targets of c5_scheduled, per unit time (the vehicles drive at 0.5)
+
+
+def c5_scheduled(ids, rows, N=30, seed=100, circle=True, goals=True, backend=None, device=0, scenario_kernels="ext"):
+    """The scheduled C5 set: the 3-player unicycle problem of C5 with a world that moves over the receding-horizon loop.
+    Returns (problem, schedule): schedule = {kind: (rows, B, len)} for mpc_solve(problem, steps, schedule=...), row t = the world at
+    MPC step t (time t dt), the last row held.
+
+    circle: one circle per game (every player must stay outside it) crosses the vehicles' paths along a straight line.  It starts
+      0.35 beside the point at radius 0.6 of player 0's way to the centre and moves at 0.2 ... 0.3 per unit time across that way, on a
+      line turned by up to 0.3 rad, both by the seed: it reaches the way about when the vehicle does.  Radius 0.1.  The problem is built
+      with the circle of row 0.
+    goals: every target moves along a line of its own -- direction by the seed -- at GOAL_SPEED per unit time, the heading of the target with it.
+    The speeds are low against the vehicles' 0.5, so every solve of the loop stays a warm-started one."""
+    ids = np.asarray(ids, dtype=np.int64)
+    model, N, dt, x0, obj, con, opts = c3_unicycle(ids, N=N, seed=seed, p=3)
+    B, p = len(ids), 3
+    t = dt * np.arange(rows)[:, None, None]                                             # (rows, 1, 1)
+    u = _uniform(seed + 7, ids, 3 + p, 0.0, 1.0)                                         # (B, 3 + p)
+    schedule = {}
+    if circle:
+        a0 = np.arctan2(x0[:, p], x0[:, 0])                                              # player 0 starts at (cos a0, sin a0) and heads for the centre
+        side = np.where(u[:, 0] < 0.5, -1.0, 1.0)
+        nrm = a0 + side * (0.5 * np.pi + 0.6 * (u[:, 1] - 0.5))                          # from the way to the circle's start
+        c0 = 0.6 * np.stack([np.cos(a0), np.sin(a0)], axis=1) + 0.35 * np.stack([np.cos(nrm), np.sin(nrm)], axis=1)
+        vel = -(0.2 + 0.1 * u[:, 2])[:, None] * np.stack([np.cos(nrm), np.sin(nrm)], axis=1)
+        c = c0[None] + t * vel[None]                                                     # (rows, B, 2)
+        schedule["circle"] = np.concatenate([c, np.full((rows, B, 1), 0.1)], axis=2)     # xc yc r
+        host.add_circle_constraint(con, c0[:1, 0].copy(), c0[:1, 1].copy(), np.array([0.1]))
+    if goals:
+        xf = np.broadcast_to(obj.xf, (rows, B, p, 4)).copy()
+        dirn = 2 * np.pi * u[:, 3:3 + p]                                                 # (B, p)
+        xf[..., 0] += GOAL_SPEED * t * np.cos(dirn)[None]
+        xf[..., 1] += GOAL_SPEED * t * np.sin(dirn)[None]
+        xf[..., 2] = np.arctan2(xf[..., 1] - x0[None, :, p:2 * p], xf[..., 0] - x0[None, :, 0:p])
+        uf = np.broadcast_to(obj.uf, (rows, B, p, 2))
+        schedule["lqr_target"] = np.concatenate([xf.reshape(rows, B, -1), uf.reshape(rows, B, -1)], axis=2)
+    prob = host.GameProblem(N, dt, x0, model, opts, obj, con, backend=backend, device=device, game_id0=int(ids[0]), scenario_kernels=scenario_kernels)
+    return prob, schedule
+
+
 def make_problem(cfg, ids, backend=None, device=0, devices=None, **kw):
     """cfg in {'C2','C3','C4','C5'} (BASELINE configurations) or 'Q' (quadrotors) -> GameProblem over the scenarios `ids`
     (global scenario ids).  devices=[...]: a sharding.ShardedGameProblem, the batch split contiguously over those devices."""

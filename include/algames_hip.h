@@ -435,6 +435,30 @@ int alg_mpc_totals(alg_handle* h, int64_t* newton_iters /*B or NULL*/, int64_t* 
  * with alg_mpc_advance.  states: NULL (asynchronous launch) or host array (steps+1) x B x n receiving x0 before the loop
  * and after every step (synchronous). */
 int alg_mpc_solve(alg_handle* h, int32_t steps, int64_t game_id0, double* states);
+/* Schedules: values per game AND per MPC step of the numbers that may differ per game, applied inside alg_mpc_solve's single launch --
+ * a goal that moves, an obstacle that follows a predicted path -- with the result the step-wise calls give (alg_set_scenario_data /
+ * alg_set_lqr with the step's row, alg_newton_solve_async, alg_mpc_advance, once per step).
+ *   kind: an ALG_SCEN_* value (len = alg_scenario_data_len(kind)) or ALG_SCHED_LQR_TARGET (len = p*ni + p*mi: xf (p x ni) | uf (p x mi)).
+ *   data: rows x B x len, step-major; NULL drops the kind's schedule.
+ *   - in step t (0-based within the call) of alg_mpc_solve game g solves with row min(t, rows - 1) of every scheduled kind: the last row is
+ *     held.  The values hold for the whole horizon of that solve (the numbers are constant over a solve, as everywhere).
+ *   - after the call the handle's per-game values of a scheduled kind are the row the last step used, on the device and in what
+ *     alg_get_scenario_data returns.
+ *   - only alg_mpc_solve reads schedules; every other entry point ignores them.
+ *   - setting the schedule of a scenario kind makes the kind per game exactly as alg_set_scenario_data(kind, row 0) does (kernel switch and
+ *     re-created multipliers in the default ALG_SCEN_KERNELS_EXT mode on the first per-game call, ALG_ERR_STATE if the kind was not added).
+ *     ALG_SCHED_LQR_TARGET needs per-game LQR data (alg_set_lqr with per_game = 1; ALG_ERR_STATE otherwise); Qd and Rd stay as set.
+ *   - every row is checked by the rules of alg_set_scenario_data (targets: finite); rows < 1 with data is refused.  On any failure the
+ *     call returns ALG_ERR_ARG and nothing changes.
+ *   - any adder (alg_add_*) drops ALL schedules, alg_set_scenario_data(kind, ...) drops the schedule of that kind, alg_set_lqr the
+ *     target schedule.
+ *   - in ALG_SCEN_KERNELS_BASE mode the block-reading twins of the base kernels read the game's block through the constant address space,
+ *     which must not change during a kernel: a schedule of a base kind (0 .. 2) on such a handle gets ALG_ERR_ARG -- use the default
+ *     mode.  ALG_SCHED_LQR_TARGET works in both modes.
+ * alg_mpc_get_schedule: *rows = the rows of the kind's schedule, 0 = none. */
+#define ALG_SCHED_LQR_TARGET 100
+int alg_mpc_set_schedule(alg_handle* h, int32_t kind, int32_t rows, const double* data /* rows x B x len, step-major; NULL = drop */);
+int alg_mpc_get_schedule(alg_handle* h, int32_t kind, int32_t* rows /* 0 = none */);
 
 #ifdef __cplusplus
 }
