@@ -22,6 +22,7 @@ ALG_ERR_ARG, ALG_ERR_DEVICE, ALG_ERR_STATE = -1, -2, -3
 ALG_SCEN_KERNELS_EXT, ALG_SCEN_KERNELS_BASE = 0, 1
 SCEN_KERNELS = ("ext", "base")
 ALG_SCHED_LQR_TARGET = 100      # alg_mpc_set_schedule: xf (p, ni) | uf (p, mi) per MPC step and game
+ALG_SCHED_DISTURBANCE = 101     # alg_mpc_set_schedule: w (n) per MPC step and game, added to the advanced state
 SCEN_KINDS = ("collision_radius", "collision_cost", "control_bound", "state_bound", "wall", "circle", "wall3d", "cylinder")
 
 
@@ -152,11 +153,12 @@ SIGNATURES = {
     "get_scenario_kernels": (C.c_int, [_P, _I, _I]),
     "mpc_set_schedule": (C.c_int, [_P, C.c_int32, C.c_int32, _D]),
     "mpc_get_schedule": (C.c_int, [_P, C.c_int32, _I]),
+    "mpc_solve_log": (C.c_int, [_P, C.c_int32, C.c_int64, _D, _D, _P]),
 }
 # Entry points a backend may lack (the CPU oracle has no per-game scenario data): bound when present; calling one that is absent
 # raises AlgamesError naming the backend.
 OPTIONAL = frozenset({"scenario_data_len", "set_scenario_data", "get_scenario_data", "set_scenario_kernels", "get_scenario_kernels",
-                      "mpc_set_schedule", "mpc_get_schedule"})
+                      "mpc_set_schedule", "mpc_get_schedule", "mpc_solve_log"})
 
 
 class AlgamesError(RuntimeError):
@@ -611,20 +613,34 @@ class Batch:
         self.lib.check(self.lib.mpc_solve(self.h, int(steps), int(game_id0), _dptr(states)))
         return states
 
+    def mpc_solve_log(self, steps, game_id0=0, states=True, controls=True, stats=True):
+        """alg_mpc_solve_log: the loop of mpc_solve with the closed-loop log.  Returns (states (steps+1, B, n), controls (steps, B, m),
+        stats (steps, B) of game_stats_dtype), None for every part not asked for; asynchronous if none is."""
+        steps = int(steps)
+        st = np.empty((steps + 1, self.B, self.n)) if states else None
+        uc = np.empty((steps, self.B, self.m)) if controls else None
+        gs = np.zeros((steps, self.B), dtype=game_stats_dtype) if stats else None
+        self.lib.check(self.lib.mpc_solve_log(self.h, steps, int(game_id0), _dptr(st), _dptr(uc), None if gs is None else gs.ctypes.data_as(_P)))
+        return st, uc, gs
+
     # ---- schedules of the fused loop (alg_mpc_set_schedule) ----------------------------------
     def _sched_kind(self, kind):
-        """(ABI kind, doubles per game and row) of a schedule kind: "lqr_target" / ALG_SCHED_LQR_TARGET or a scenario kind."""
+        """(ABI kind, doubles per game and row) of a schedule kind: "lqr_target" / ALG_SCHED_LQR_TARGET, "disturbance" /
+        ALG_SCHED_DISTURBANCE or a scenario kind."""
+        if kind == "disturbance" or (not isinstance(kind, str) and int(kind) == ALG_SCHED_DISTURBANCE):
+            return ALG_SCHED_DISTURBANCE, self.n
         if kind == "lqr_target" or (not isinstance(kind, str) and int(kind) == ALG_SCHED_LQR_TARGET):
             return ALG_SCHED_LQR_TARGET, self.p * self.ni + self.p * self.mi
         if isinstance(kind, str) and kind not in SCEN_KINDS:
-            raise ValueError(f"unknown schedule kind {kind!r}; 'lqr_target' or one of {SCEN_KINDS}")
+            raise ValueError(f"unknown schedule kind {kind!r}; 'lqr_target', 'disturbance' or one of {SCEN_KINDS}")
         k = self._kind(kind)
         return k, self.scenario_data_len(k)
 
     def mpc_set_schedule(self, kind, data):
         """Values per MPC step and game of one kind for mpc_solve: data (rows, B, len), step t of the loop takes row min(t, rows - 1);
         None drops the kind's schedule.  kind: a scenario kind (name in SCEN_KINDS or ALG_SCEN_* value; len = scenario_data_len(kind)) or
-        "lqr_target" (len = p ni + p mi: xf (p, ni) | uf (p, mi) of every game).  See alg_mpc_set_schedule."""
+        "lqr_target" (len = p ni + p mi: xf (p, ni) | uf (p, mi) of every game) or "disturbance" (len = n: added to the advanced state of
+        every step, finite).  See alg_mpc_set_schedule."""
         k, L = self._sched_kind(kind)
         if data is None:
             self.lib.check(self.lib.mpc_set_schedule(self.h, k, 0, None))
@@ -632,8 +648,11 @@ class Batch:
         a = np.ascontiguousarray(np.asarray(data, dtype=np.float64))
         if a.ndim != 3 or a.shape[0] < 1 or a.shape[1:] != (self.B, L):
             raise ValueError(f"schedule of kind {kind!r}: expected shape (rows >= 1, {self.B}, {L}), got {a.shape}")
+        if k == ALG_SCHED_DISTURBANCE and not np.all(np.isfinite(a)):
+            raise ValueError(f"schedule of kind {kind!r}: every entry must be finite (row {int(np.argwhere(~np.isfinite(a))[0][0])})")
         self.lib.check(self.lib.mpc_set_schedule(self.h, k, a.shape[0], _dptr(a)))
-        self._refresh_con_len()
+        if k != ALG_SCHED_DISTURBANCE:
+            self._refresh_con_len()
 
     def mpc_get_schedule(self, kind):
         """Rows of the kind's schedule, 0 = none."""

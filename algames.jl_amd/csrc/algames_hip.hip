@@ -193,6 +193,7 @@ struct Handle {
         std::vector<double> data;     // host copies: the row the last step used goes into the host mirrors after a loop
         std::vector<int> map;
     } sched[ALG_SCHED_MAX_KINDS];
+    Sched dist;                   // the plant disturbance (ALG_SCHED_DISTURBANCE): rows x B x n, no block offsets; rows = 0: none
     bool keep_sched = false;      // set while alg_set_scenario_data's own switch to the EXT kernels runs (it is no adder: schedules stay)
 };
 
@@ -259,8 +260,7 @@ void dfree(Handle* h, void* q) {
 }
 
 // schedules of alg_mpc_solve (alg_mpc_set_schedule): dropping one frees its device copies
-void sched_drop(Handle* hd, int slot) {
-    Handle::Sched& sc = hd->sched[slot];
+void sched_drop(Handle* hd, Handle::Sched& sc) {
     if (!sc.rows) return;
     hipSetDevice(hd->device);
     hipStreamSynchronize(hd->stream);              // a loop that reads the schedule may still run
@@ -268,7 +268,8 @@ void sched_drop(Handle* hd, int slot) {
     if (sc.d_map) dfree(hd, sc.d_map);
     sc = Handle::Sched();
 }
-void sched_drop_all(Handle* hd) { for (int k = 0; k < ALG_SCHED_MAX_KINDS; k++) sched_drop(hd, k); }
+void sched_drop(Handle* hd, int slot) { sched_drop(hd, hd->sched[slot]); }
+void sched_drop_all(Handle* hd) { for (int k = 0; k < ALG_SCHED_MAX_KINDS; k++) sched_drop(hd, k); sched_drop(hd, hd->dist); }
 
 // strided copies between the dense host layout (B x width) and a per-game segment of an arena (pitch = arena stride)
 int h2d_seg(Handle* h, double* dseg, size_t dpitch_d, const void* src, size_t width_bytes) {
@@ -393,7 +394,7 @@ int launch_mpc_loop(Handle* h, int steps, uint64_t game_id0, double* d_states) {
     return launch_check("k_mpc_loop (team)");
 }
 // ... with the handle's schedules (alg_mpc_set_schedule): the sibling kernels, same shapes
-int launch_mpc_loop_sched(Handle* h, int steps, uint64_t game_id0, double* d_states) {
+int launch_mpc_loop_sched(Handle* h, int steps, uint64_t game_id0, double* d_states, double* d_controls, alg_game_stats* d_stats) {
     const int nw = team_width(h);
     if (nw < 0) return fail(ALG_ERR_ARG, "alg_set_waves_per_game: no team kernel of that width is compiled for this configuration");
     MpcSched sd; std::memset(&sd, 0, sizeof(sd));
@@ -403,10 +404,13 @@ int launch_mpc_loop_sched(Handle* h, int steps, uint64_t game_id0, double* d_sta
         MpcSchedKind& d = sd.k[sd.nk++];
         d.data = sc.d_data; d.map = sc.d_map; d.rows = sc.rows; d.len = sc.len;
     }
-    if (nw == 1) { LAUNCH(k_mpc_loop_sched, h->pr, steps, game_id0, d_states, sd); return ALG_OK; }
+    MpcLoopLog lg; std::memset(&lg, 0, sizeof(lg));
+    lg.controls = d_controls; lg.stats = d_stats;
+    if (h->dist.rows) { lg.dist = h->dist.d_data; lg.dist_rows = h->dist.rows; }
+    if (nw == 1) { LAUNCH(k_mpc_loop_sched, h->pr, steps, game_id0, d_states, sd, lg); return ALG_OK; }
     const Params& pr = h->pr; bool done = false;
 #define X(M, P, D, E, W) if (!done && nw == (W) && pr.model == (M) && pr.p == (P) && pr.d == (D) && pr.ext == (E)) {                   \
-        hipLaunchKernelGGL((k_mpc_loop_sched<Cfg<M, P, D, E, W>>), dim3(pr.B), dim3(WAVE * (W)), 0, h->stream, h->pr, steps, game_id0, d_states, sd); done = true; }
+        hipLaunchKernelGGL((k_mpc_loop_sched<Cfg<M, P, D, E, W>>), dim3(pr.B), dim3(WAVE * (W)), 0, h->stream, h->pr, steps, game_id0, d_states, sd, lg); done = true; }
     ALG_CFGS_MW(X)
     ALG_CFGS_MW_SCEN(X)
     ALG_CFGS_MW_DENSE(X)
@@ -1340,17 +1344,27 @@ int alg_mpc_advance(alg_handle* h) {
     LAUNCH(k_mpc_advance, H->pr);
     return ALG_OK;
 }
-int alg_mpc_solve(alg_handle* h, int32_t steps, int64_t game_id0, double* states) {
-    if (!h || steps < 1) return fail(ALG_ERR_ARG, "alg_mpc_solve: bad argument");
+} // extern "C"
+// The loop of alg_mpc_solve and alg_mpc_solve_log; `who` names the entry point in the error messages
+static int mpc_solve_impl(const char* who, alg_handle* h, int32_t steps, int64_t game_id0, double* states, double* controls, alg_game_stats* stats) {
+    if (!h || steps < 1) return fail(ALG_ERR_ARG, std::string(who) + ": bad argument");
     int rc = use_device(H); if (rc) return rc;
-    if (!H->x0_set || !H->lqr_set) return fail(ALG_ERR_STATE, "alg_mpc_solve: x0 / LQR data not set");
+    if (!H->x0_set || !H->lqr_set) return fail(ALG_ERR_STATE, std::string(who) + ": x0 / LQR data not set");
     const Params& p = H->pr;
-    const size_t cnt = (size_t)(steps + 1) * p.B * p.n;
-    if (states && (rc = ensure_scratch(H, sizeof(double) * cnt))) return rc;
+    // one scratch allocation for all requested outputs: [states | controls | stats], every part 8-byte aligned
+    const size_t b_st = states ? sizeof(double) * (size_t)(steps + 1) * p.B * p.n : 0, b_uc = controls ? sizeof(double) * (size_t)steps * p.B * p.m : 0,
+                 b_gs = stats ? sizeof(alg_game_stats) * (size_t)steps * p.B : 0;
+    static_assert(sizeof(alg_game_stats) % 8 == 0, "the stats log follows doubles in the scratch");
+    if (b_st + b_uc + b_gs && (rc = ensure_scratch(H, b_st + b_uc + b_gs))) return rc;
+    char* const d0 = (char*)H->d_scratch;
+    double* const d_states = states ? (double*)d0 : nullptr;
+    double* const d_controls = controls ? (double*)(d0 + b_st) : nullptr;
+    alg_game_stats* const d_stats = stats ? (alg_game_stats*)(d0 + b_st + b_uc) : nullptr;
     bool scheduled = false;
     for (int k = 0; k < ALG_SCHED_MAX_KINDS; k++) scheduled |= H->sched[k].rows > 0;
-    if (!scheduled) rc = launch_mpc_loop(H, (int)steps, (uint64_t)game_id0, states ? (double*)H->d_scratch : (double*)nullptr);
-    else rc = launch_mpc_loop_sched(H, (int)steps, (uint64_t)game_id0, states ? (double*)H->d_scratch : (double*)nullptr);
+    // the sibling kernels are the loop with per-step phases: a schedule, a disturbance or a log takes them
+    if (!scheduled && !H->dist.rows && !controls && !stats) rc = launch_mpc_loop(H, (int)steps, (uint64_t)game_id0, d_states);
+    else rc = launch_mpc_loop_sched(H, (int)steps, (uint64_t)game_id0, d_states, d_controls, d_stats);
     if (rc) return rc;
     // the loop leaves the row its last step used in the games' blocks: the host mirror of the scenario blocks follows (what the step-wise
     // alg_set_scenario_data calls would have left; the LQR blocks have no host mirror)
@@ -1362,15 +1376,46 @@ int alg_mpc_solve(alg_handle* h, int32_t steps, int64_t game_id0, double* states
             for (int e = 0; e < sc.len; e++)
                 if (sc.map[e] >= 0) H->scen_games[g * SS + sc.map[e]] = sc.data[(row * p.B + g) * sc.len + e];
     }
-    if (states) return d2h(H, states, H->d_scratch, sizeof(double) * cnt);
+    // one copy back per output (each waits for the stream: the call is synchronous as soon as one output is asked for)
+    if (states && (rc = d2h(H, states, d_states, b_st))) return rc;
+    if (controls && (rc = d2h(H, controls, d_controls, b_uc))) return rc;
+    if (stats && (rc = d2h(H, stats, d_stats, b_gs))) return rc;
     return ALG_OK;
 }
+extern "C" {
+int alg_mpc_solve(alg_handle* h, int32_t steps, int64_t game_id0, double* states) {
+    return mpc_solve_impl("alg_mpc_solve", h, steps, game_id0, states, nullptr, nullptr);
+}
+// ... with the closed-loop log: the control applied and the statistics of every step (include/algames_hip.h)
+int alg_mpc_solve_log(alg_handle* h, int32_t steps, int64_t game_id0, double* states, double* controls, alg_game_stats* stats) {
+    return mpc_solve_impl("alg_mpc_solve_log", h, steps, game_id0, states, controls, stats);
+}
+} // extern "C"
+// The plant disturbance (ALG_SCHED_DISTURBANCE): rows x B x n, needs nothing of the handle but its sizes
+static int set_disturbance(Handle* hd, int32_t rows, const double* data) {
+    int rc = use_device(hd); if (rc) return rc;
+    if (!data) { sched_drop(hd, hd->dist); return ALG_OK; }
+    if (rows < 1) return fail(ALG_ERR_ARG, "alg_mpc_set_schedule: rows must be >= 1");
+    const Params& p = hd->pr;
+    const size_t per_row = (size_t)p.B * p.n, cnt = (size_t)rows * per_row;
+    for (size_t e = 0; e < cnt; e++)
+        if (!std::isfinite(data[e])) return fail(ALG_ERR_ARG, "alg_mpc_set_schedule: row " + std::to_string(e / per_row) + ": disturbances must be finite");
+    Handle::Sched sc;
+    sc.rows = rows; sc.len = p.n;
+    if ((rc = dalloc(hd, &sc.d_data, cnt, "disturbance rows"))) return rc;
+    if ((rc = h2d(hd, sc.d_data, data, sizeof(double) * cnt))) { dfree(hd, sc.d_data); return rc; }
+    sched_drop(hd, hd->dist);
+    hd->dist = std::move(sc);
+    return ALG_OK;
+}
+extern "C" {
 // Schedules of alg_mpc_solve: per game and per MPC step values of one kind (include/algames_hip.h)
 int alg_mpc_set_schedule(alg_handle* h, int32_t kind, int32_t rows, const double* data) {
     static const char* who = "alg_mpc_set_schedule";
     NEED_HANDLE("alg_mpc_set_schedule");
+    if (kind == ALG_SCHED_DISTURBANCE) return set_disturbance(H, rows, data);
     const bool target = kind == ALG_SCHED_LQR_TARGET;
-    if (!target && !scen_kind_ok(kind)) return fail(ALG_ERR_ARG, "alg_mpc_set_schedule: unknown kind (an ALG_SCEN_* value or ALG_SCHED_LQR_TARGET)");
+    if (!target && !scen_kind_ok(kind)) return fail(ALG_ERR_ARG, "alg_mpc_set_schedule: unknown kind (an ALG_SCEN_* value, ALG_SCHED_LQR_TARGET or ALG_SCHED_DISTURBANCE)");
     const int slot = target ? ALG_SCHED_MAX_KINDS - 1 : (int)kind;
     int rc = use_device(H); if (rc) return rc;
     if (!data) { sched_drop(H, slot); return ALG_OK; }
@@ -1420,7 +1465,8 @@ int alg_mpc_set_schedule(alg_handle* h, int32_t kind, int32_t rows, const double
 }
 int alg_mpc_get_schedule(alg_handle* h, int32_t kind, int32_t* rows) {
     if (!h || !rows) return fail(ALG_ERR_ARG, "alg_mpc_get_schedule: null argument");
-    if (kind != ALG_SCHED_LQR_TARGET && !scen_kind_ok(kind)) return fail(ALG_ERR_ARG, "alg_mpc_get_schedule: unknown kind (an ALG_SCEN_* value or ALG_SCHED_LQR_TARGET)");
+    if (kind == ALG_SCHED_DISTURBANCE) { *rows = H->dist.rows; return ALG_OK; }
+    if (kind != ALG_SCHED_LQR_TARGET && !scen_kind_ok(kind)) return fail(ALG_ERR_ARG, "alg_mpc_get_schedule: unknown kind (an ALG_SCEN_* value, ALG_SCHED_LQR_TARGET or ALG_SCHED_DISTURBANCE)");
     *rows = H->sched[kind == ALG_SCHED_LQR_TARGET ? ALG_SCHED_MAX_KINDS - 1 : (int)kind].rows;
     return ALG_OK;
 }

@@ -251,7 +251,8 @@ __global__ void __launch_bounds__(C::NT, mpc_loop_wpe<C>) k_mpc_loop(Params pr_a
 // The receding-horizon loop with a SCHEDULE (alg_mpc_set_schedule): per game and per MPC step values of the numbers that may differ per
 // game -- the kinds of the scenario block and the LQR targets xf / uf.  A sibling of k_mpc_loop, not one more argument of it: k_mpc_loop's
 // source, and with it the binary of every unscheduled loop, stays what it was; the siblings live in translation units of
-// their own (algames_sched.hip) and are launched only while the handle carries a schedule.
+// their own (algames_sched.hip) and are launched only while the handle carries a schedule or a disturbance, or the call asks for a log
+// (alg_mpc_solve_log): the sibling is the loop with per-step phases.
 // The schedule sits in device memory in compact form, rows x B x len doubles per kind, with a table of len block offsets per kind (the host's
 // scen_map; ALG_SCHED_TO_LQR marks an offset into the game's LQR block, a negative entry is skipped like alg_set_scenario_data skips it).
 // Before every solve the game's wavefronts copy row min(t, rows - 1) of every kind into the game's own blocks with ordinary vector stores.
@@ -262,7 +263,11 @@ constexpr int ALG_SCHED_MAX_KINDS = 9;                 // the eight ALG_SCEN_* k
 constexpr int ALG_SCHED_TO_LQR = 1 << 30;
 struct MpcSchedKind { const double* data; const int* map; int rows, len; };
 struct MpcSched { int nk, pad_; MpcSchedKind k[ALG_SCHED_MAX_KINDS]; };
-struct MpcLoopSchedArgs { Params pr; int steps; uint64_t game_id0; double* states; MpcSched sd; };
+// The per-step phases besides the schedule (alg_mpc_solve_log, ALG_SCHED_DISTURBANCE): the LOG of step t -- the control the advance
+// applies (u_1 of pdtraj, the m doubles behind x_2) and the game's alg_game_stats as the solve left them -- and the plant DISTURBANCE
+// w[min(t, rows - 1)][g], added to the advanced state.  A null pointer skips its part.  Descriptors of their own in the kernel-argument segment.
+struct MpcLoopLog { double* controls; alg_game_stats* stats; const double* dist; int dist_rows, pad_; };
+struct MpcLoopSchedArgs { Params pr; int steps; uint64_t game_id0; double* states; MpcSched sd; MpcLoopLog lg; };
 template <class C>
 __device__ __forceinline__ void mpc_apply_schedule(CPR pr, const ALG_AS4 MpcSched& sd, const int g, const int t) {
     const int tid = phase_lane(), nk = sd.nk;
@@ -280,8 +285,34 @@ __device__ __forceinline__ void mpc_apply_schedule(CPR pr, const ALG_AS4 MpcSche
         }
     }
 }
+// the log phase: after the solve of step t, before the advance (which shifts nothing but x0 / x_1, yet the totals belong to the same step)
 template <class C>
-__global__ void __launch_bounds__(C::NT, mpc_loop_wpe<C>) k_mpc_loop_sched(Params pr_arg, int steps_arg, uint64_t game_id0_arg, double* states_arg, MpcSched sd_arg) {
+__device__ __forceinline__ void mpc_log_step(CPR pr, const Game& G, const ALG_AS4 MpcLoopLog& lg, const int g, const int t) {
+    const int tid = phase_lane();
+    const size_t at = (size_t)t * pr.B + g;
+    double* const uc = lg.controls;
+    if (uc && tid < C::m) as_global(uc)[at * C::m + tid] = G.z(0)[2 * C::n + tid];
+    alg_game_stats* const so = lg.stats;
+    constexpr int W = (int)(sizeof(alg_game_stats) / 8);
+    static_assert(sizeof(alg_game_stats) % 8 == 0, "alg_game_stats is copied in 8-byte words");
+    if (so && tid < W) reinterpret_cast<unsigned long long*>(as_global(so) + at)[tid] = reinterpret_cast<const unsigned long long*>(G.st(pr))[tid];
+}
+// the disturbance phase: after the advance, x0 <- x0 + w_t with one double addition per entry on the STORED x0 (the sum the host forms in the
+// step-wise definition: alg_set_x0(x_1 + w_t)), written to the three places alg_set_x0 writes.  Not part of mpc_advance, nor of its RK2
+// expression: the unscheduled kernels share that function, and a sum folded into it would round differently.
+template <class C>
+__device__ __forceinline__ void mpc_disturb(CPR pr, const Game& G, const ALG_AS4 MpcLoopLog& lg, const int g, const int t) {
+    const double* const w = lg.dist;
+    if (!w) return;
+    const int tid = phase_lane(), rows = lg.dist_rows, row = t < rows ? t : rows - 1;      // the last row is held
+    if (tid < C::n) {
+        const double v = G.x0w(pr)[tid] + as_global(w)[((size_t)row * pr.B + g) * C::n + tid];
+        G.x0w(pr)[tid] = v; G.z(0)[tid] = v; G.z(1)[tid] = v;
+    }
+}
+template <class C>
+__global__ void __launch_bounds__(C::NT, mpc_loop_wpe<C>) k_mpc_loop_sched(Params pr_arg, int steps_arg, uint64_t game_id0_arg, double* states_arg, MpcSched sd_arg,
+                                                                            MpcLoopLog lg_arg) {
     __shared__ Lds<C> L;
     CPR pr = kernel_params();
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -306,7 +337,12 @@ __global__ void __launch_bounds__(C::NT, mpc_loop_wpe<C>) k_mpc_loop_sched(Param
         const int gq = phase_int(g);
         newton_solve<C, 0, mpc_loop_launder_v<C>>(pr, G, L, 1, kq().game_id0 + (uint64_t)t * 1000003ull + (uint64_t)gq, t == 0 ? -1 : 1, t == 0 ? -1 : 0);
         __syncthreads();
+        // the log phase, the advance, the disturbance phase: each behind a barrier, each from the opaque roots like the schedule phase
+        mpc_log_step<C>(phase_params(pr), G.fresh(), kq().lg, phase_int(g), t);
+        __syncthreads();
         mpc_advance<C>(phase_params(pr), G.fresh());
+        __syncthreads();
+        mpc_disturb<C>(phase_params(pr), G.fresh(), kq().lg, phase_int(g), t);
         __syncthreads();
         double* const states = kq().states;
         const int ln = phase_lane();
@@ -478,8 +514,8 @@ __global__ void __launch_bounds__(C::NT, mpc_loop_wpe<C>) k_mpc_loop_sched(Param
 #define ALG_DEFINE_KERNELS(M, P, D, E) ALG_INSTANTIATE_KERNELS(template, M, P, D, E)
 #define ALG_DECLARE_KERNELS(M, P, D, E) ALG_INSTANTIATE_KERNELS(extern template, M, P, D, E)
 // The scheduled receding-horizon loops (k_mpc_loop_sched): one per loop kernel of the lists above, defined in algames_sched.hip
-#define ALG_INSTANTIATE_SCHED(PREFIX, M, P, D, E) PREFIX __global__ void k_mpc_loop_sched<Cfg<M, P, D, E>>(Params, int, uint64_t, double*, MpcSched);
-#define ALG_INSTANTIATE_SCHED_MW(PREFIX, M, P, D, E, W) PREFIX __global__ void k_mpc_loop_sched<Cfg<M, P, D, E, W>>(Params, int, uint64_t, double*, MpcSched);
+#define ALG_INSTANTIATE_SCHED(PREFIX, M, P, D, E) PREFIX __global__ void k_mpc_loop_sched<Cfg<M, P, D, E>>(Params, int, uint64_t, double*, MpcSched, MpcLoopLog);
+#define ALG_INSTANTIATE_SCHED_MW(PREFIX, M, P, D, E, W) PREFIX __global__ void k_mpc_loop_sched<Cfg<M, P, D, E, W>>(Params, int, uint64_t, double*, MpcSched, MpcLoopLog);
 #define ALG_DEFINE_SCHED(M, P, D, E) ALG_INSTANTIATE_SCHED(template, M, P, D, E)
 #define ALG_DECLARE_SCHED(M, P, D, E) ALG_INSTANTIATE_SCHED(extern template, M, P, D, E)
 #define ALG_DEFINE_SCHED_MW(M, P, D, E, W) ALG_INSTANTIATE_SCHED_MW(template, M, P, D, E, W)

@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import (ALG_MODEL_BICYCLE, ALG_MODEL_DOUBLE_INTEGRATOR, ALG_MODEL_QUADROTOR, ALG_MODEL_UNICYCLE, ALG_TRAJ_PD, ALG_TRAJ_TRIAL,
-                   ALG_TRAJ_DELTA, ALG_SCHED_LQR_TARGET, AlgamesError, Batch, CLib)
+                   ALG_TRAJ_DELTA, ALG_SCHED_LQR_TARGET, ALG_SCHED_DISTURBANCE, AlgamesError, Batch, CLib)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.environ.get("ALGAMES_HIP_LIB", os.path.join(_HERE, "lib", "libalgames_hip.so"))
@@ -1033,6 +1033,39 @@ def ibr_newton_solve(prob, i=None, ibr_opts=None, init=True):
 # `opts.shift` / `opts.dual_reset` (options.jl:16-17, primal_dual_traj.jl:35-39, solver_methods.jl:25).  Builder-defined
 # (SURVEY.md 8(d) C5): solve; x0 <- RK2(x_1, u_1); next solve warm-started with shift = 1 and dual_reset = false.
 # --------------------------------------------------------------------------------------------------
+def _mpc_schedule(b, schedule):
+    """{kind: array (rows, B, len)} -> [(ABI kind, array)] in kind order, shapes checked before any library call"""
+    sched = []
+    for kind in (schedule or {}):
+        k, L = b._sched_kind(kind)
+        if k == ALG_SCHED_DISTURBANCE:
+            raise ValueError(f"schedule of kind {kind!r}: the disturbance is no entry of `schedule`: it is the `disturbance` argument of mpc_rollout; "
+                             "for mpc_solve upload it with Batch.mpc_set_schedule('disturbance', w) before the call")
+        a = np.ascontiguousarray(np.asarray(schedule[kind], dtype=np.float64))
+        if a.ndim != 3 or a.shape[0] < 1 or a.shape[1:] != (b.B, L):
+            raise ValueError(f"schedule of kind {kind!r}: expected shape (rows >= 1, {b.B}, {L}), got {a.shape}")
+        sched.append((k, a))
+    sched.sort(key=lambda ka: ka[0])
+    return sched
+
+
+def _apply_schedule_rows(prob, sched, t):
+    """the step-wise definition of the schedule: row min(t, rows - 1) of every kind through set_scenario_data / set_lqr"""
+    b = prob.batch
+    for k, a in sched:
+        r = min(t, a.shape[0] - 1)
+        if t > 0 and r == min(t - 1, a.shape[0] - 1):
+            continue                            # the last row is held: nothing to upload
+        if k == ALG_SCHED_LQR_TARGET:
+            obj = prob.game_obj
+            if np.ndim(obj.Qdiag) != 3:
+                raise AlgamesError("mpc_solve: a target schedule needs per-game LQR data (Qdiag, Rdiag of shape (B, p, .))")
+            w = b.p * b.ni
+            b.set_lqr(obj.Qdiag, obj.Rdiag, a[r][:, :w].reshape(b.B, b.p, b.ni), a[r][:, w:].reshape(b.B, b.p, b.mi))
+        else:
+            b.set_scenario_data(k, a[r])
+
+
 def mpc_solve(prob, steps, record_states=False, fused=True, schedule=None):
     """Runs `steps` receding-horizon solves for every game of the batch.  Returns (newton_iters (B,), converged (B,),
     states (steps+1, B, n) or None).  fused=True: one launch, every game runs its own loop (alg_mpc_solve); fused=False:
@@ -1045,14 +1078,7 @@ def mpc_solve(prob, steps, record_states=False, fused=True, schedule=None):
     again; fused=False applies the step's rows through set_scenario_data / set_lqr before each step's solve -- the definition the fused
     path is held to.  Either way the handle keeps the rows the last step used."""
     b = prob.batch
-    sched = []
-    for kind in (schedule or {}):
-        k, L = b._sched_kind(kind)
-        a = np.ascontiguousarray(np.asarray(schedule[kind], dtype=np.float64))
-        if a.ndim != 3 or a.shape[0] < 1 or a.shape[1:] != (b.B, L):
-            raise ValueError(f"schedule of kind {kind!r}: expected shape (rows >= 1, {b.B}, {L}), got {a.shape}")
-        sched.append((k, a))
-    sched.sort(key=lambda ka: ka[0])
+    sched = _mpc_schedule(b, schedule)
     b.mpc_totals(reset=True)
     prob._sync_options()
     if fused:
@@ -1068,25 +1094,12 @@ def mpc_solve(prob, steps, record_states=False, fused=True, schedule=None):
     shift0, reset0 = prob.opts.shift, prob.opts.dual_reset
     states = [b.get_x0()] if record_states else None
 
-    def apply_rows(t):
-        for k, a in sched:
-            r = min(t, a.shape[0] - 1)
-            if t > 0 and r == min(t - 1, a.shape[0] - 1):
-                continue                            # the last row is held: nothing to upload
-            if k == ALG_SCHED_LQR_TARGET:
-                obj = prob.game_obj
-                if np.ndim(obj.Qdiag) != 3:
-                    raise AlgamesError("mpc_solve: a target schedule needs per-game LQR data (Qdiag, Rdiag of shape (B, p, .))")
-                w = b.p * b.ni
-                b.set_lqr(obj.Qdiag, obj.Rdiag, a[r][:, :w].reshape(b.B, b.p, b.ni), a[r][:, w:].reshape(b.B, b.p, b.mi))
-            else:
-                b.set_scenario_data(k, a[r])
     try:
         for t in range(steps):
             if t == 1:
                 prob.opts.shift, prob.opts.dual_reset = 1, False
                 prob._sync_options()
-            apply_rows(t)
+            _apply_schedule_rows(prob, sched, t)
             b.newton_solve_async(init=True, game_id0=prob.game_id0 + t * 1000003)
             b.mpc_advance()
             if record_states:
@@ -1096,3 +1109,75 @@ def mpc_solve(prob, steps, record_states=False, fused=True, schedule=None):
         prob.opts.shift, prob.opts.dual_reset = shift0, reset0
         prob._sync_options()
     return it, cv, (np.stack(states) if record_states else None)
+
+
+@dataclasses.dataclass
+class MpcRollout:
+    """Closed-loop log of mpc_rollout: states (steps+1, B, n) -- x0 before the loop and after every step, disturbed where a disturbance
+    acts --, controls (steps, B, m) -- the joint control every advance applied, player-major --, stats (steps, B) of game_stats_dtype --
+    every step's solve as get_stats reports it --, and the totals newton_iters (B,), converged (B,)."""
+    states: np.ndarray
+    controls: np.ndarray
+    stats: np.ndarray
+    newton_iters: np.ndarray
+    converged: np.ndarray
+
+
+def mpc_rollout(prob, steps, schedule=None, disturbance=None, fused=True):
+    """The receding-horizon loop as a closed-loop simulation: mpc_solve's loop with every step observable and a disturbed plant.  Returns
+    an MpcRollout.
+
+    schedule: as for mpc_solve.  disturbance: (rows, B, n), finite -- after the advance of step t the state becomes
+    x0 + disturbance[min(t, rows - 1)] (the last row is held); states[t + 1] is the disturbed state.
+    fused=True: one launch (alg_mpc_solve_log; schedule and disturbance are uploaded and dropped again); fused=False: the definition --
+    per step the schedule rows, newton_solve_async, get_stats and u_1 of get_traj, mpc_advance, x_1 read back, set_x0(x_1 + w_t)."""
+    b = prob.batch
+    steps = int(steps)
+    if steps < 1:
+        raise ValueError(f"mpc_rollout: steps must be >= 1, got {steps}")
+    sched = _mpc_schedule(b, schedule)
+    w = None
+    if disturbance is not None:
+        w = np.ascontiguousarray(np.asarray(disturbance, dtype=np.float64))
+        if w.ndim != 3 or w.shape[0] < 1 or w.shape[1:] != (b.B, b.n):
+            raise ValueError(f"disturbance: expected shape (rows >= 1, {b.B}, {b.n}), got {w.shape}")
+        if not np.all(np.isfinite(w)):
+            raise ValueError(f"disturbance: every entry must be finite (row {int(np.argwhere(~np.isfinite(w))[0][0])})")
+    b.mpc_totals(reset=True)
+    prob._sync_options()
+    if fused:
+        up = sched + ([(ALG_SCHED_DISTURBANCE, w)] if w is not None else [])
+        done = []
+        try:
+            for k, a in up:
+                b.mpc_set_schedule(k, a)
+                done.append(k)
+            states, controls, stats = b.mpc_solve_log(steps, prob.game_id0)
+            it, cv = b.mpc_totals()
+        finally:
+            for k in done:
+                b.mpc_set_schedule(k, None)
+        return MpcRollout(states, controls, stats, it, cv)
+    shift0, reset0 = prob.opts.shift, prob.opts.dual_reset
+    n, m = b.n, b.m
+    states, controls, stats = [b.get_x0()], [], []
+    try:
+        for t in range(steps):
+            if t == 1:
+                prob.opts.shift, prob.opts.dual_reset = 1, False
+                prob._sync_options()
+            _apply_schedule_rows(prob, sched, t)
+            b.newton_solve_async(init=True, game_id0=prob.game_id0 + t * 1000003)
+            stats.append(b.get_stats())
+            controls.append(b.get_traj()[:, 2 * n:2 * n + m].copy())
+            b.mpc_advance()
+            x1 = b.get_x0()
+            if w is not None:
+                x1 = x1 + w[min(t, w.shape[0] - 1)]
+                b.set_x0(x1)
+            states.append(x1)
+        it, cv = b.mpc_totals()
+    finally:
+        prob.opts.shift, prob.opts.dual_reset = shift0, reset0
+        prob._sync_options()
+    return MpcRollout(np.stack(states), np.stack(controls), np.stack(stats), it, cv)

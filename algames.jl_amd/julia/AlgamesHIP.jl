@@ -9,6 +9,7 @@
 #   newton_solve!(bp)                                 src/problem/solver_methods.jl:5-65 for every problem of the batch
 #   ibr_newton_solve!(bp; ibr_opts), ibr_newton_solve!(bp, i)     solver_methods.jl:133-228
 #   mpc_solve!(bp, steps; schedule)                   receding-horizon loop of BASELINE config 5 (opts.shift / opts.dual_reset), with per-step values of targets / obstacles
+#   mpc_solve_log!(bp, steps; disturbance)            the same loop with the closed-loop log (controls and statistics of every step) and a plant disturbance
 #   newton_solve!(probs::Vector{<:GameProblem})       convenience: build a handle, solve, release
 #   sp = ShardedGameProblem(probs; devices=0:7); newton_solve!(sp)     the batch split over several devices (one handle each)
 # After a solve every `prob.pdtraj`, the multipliers / penalties / values of every constraint (`conval.λ`, `.μ`, `.vals`,
@@ -553,7 +554,8 @@ function ibr_newton_solve!(bp::BatchedGameProblem, i::Int)
 end
 
 const SCHED_LQR_TARGET = 100       # ALG_SCHED_LQR_TARGET: xf (p x ni) | uf (p x mi) of every game and MPC step
-"ABI kind of a schedule key: an ALG_SCEN_* value (0 .. 7) or `:lqr_target`"
+const SCHED_DISTURBANCE = 101      # ALG_SCHED_DISTURBANCE: w (n) of every game and MPC step, added to the advanced state
+"ABI kind of a schedule key: an ALG_SCEN_* value (0 .. 7), `SCHED_DISTURBANCE` or `:lqr_target`"
 sched_kind(k::Integer) = Int32(k)
 sched_kind(k::Symbol) = k == :lqr_target ? Int32(SCHED_LQR_TARGET) : error("mpc_solve!: unknown schedule kind $k (:lqr_target or an ALG_SCEN_* value)")
 "rows of the kind's schedule on the handle, 0 = none (alg_mpc_get_schedule)"
@@ -561,6 +563,32 @@ function mpc_schedule_rows(bp::BatchedGameProblem, kind)
     rows = Ref{Int32}(0)
     check(ccall((:alg_mpc_get_schedule, LIB), Cint, (Ptr{Cvoid}, Int32, Ref{Int32}), bp.h, sched_kind(kind), rows))
     return Int(rows[])
+end
+
+"""
+    with_schedules(f, bp, who, schedule)
+
+Uploads every entry of `schedule` (`nothing` or a `Dict` kind => `len x B x rows` array; `alg_mpc_set_schedule`), runs `f()` and drops
+the uploaded kinds again, also when an upload or `f` throws.  Shared by `mpc_solve!` and `mpc_solve_log!`.
+"""
+function with_schedules(f, bp::BatchedGameProblem, who::String, schedule)
+    B = length(bp.probs)
+    done = Int32[]
+    try
+        if schedule !== nothing
+            for (k, V) in schedule
+                A = Array{Float64, 3}(V)
+                size(A, 2) == B && size(A, 3) >= 1 || error("$who: schedule of kind $k must be len x $B x rows")
+                check(ccall((:alg_mpc_set_schedule, LIB), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}), bp.h, sched_kind(k), size(A, 3), A))
+                push!(done, sched_kind(k))
+            end
+        end
+        return f()
+    finally
+        for k in sort!(done)
+            check(ccall((:alg_mpc_set_schedule, LIB), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}), bp.h, k, 0, C_NULL))
+        end
+    end
 end
 
 """
@@ -581,20 +609,8 @@ function mpc_solve!(bp::BatchedGameProblem, steps::Integer; game_id0::Integer=0,
     iters = zeros(Int64, B); conv = zeros(Int64, B)
     check(ccall((:alg_mpc_totals, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Int32), bp.h, iters, conv, 1))      # reset the totals
     states = zeros(n, B, steps + 1)
-    kinds = schedule === nothing ? Int32[] : sort!([sched_kind(k) for k in keys(schedule)])
-    if schedule !== nothing
-        for (k, V) in schedule
-            A = Array{Float64, 3}(V)
-            size(A, 2) == B && size(A, 3) >= 1 || error("mpc_solve!: schedule of kind $k must be len x $B x rows")
-            check(ccall((:alg_mpc_set_schedule, LIB), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}), bp.h, sched_kind(k), size(A, 3), A))
-        end
-    end
-    try
+    with_schedules(bp, "mpc_solve!", schedule) do
         check(ccall((:alg_mpc_solve, LIB), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}), bp.h, steps, game_id0, states))
-    finally
-        for k in kinds
-            check(ccall((:alg_mpc_set_schedule, LIB), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}), bp.h, k, 0, C_NULL))
-        end
     end
     check(ccall((:alg_mpc_totals, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Int32), bp.h, iters, conv, 0))
     stats = Vector{AlgGameStats}(undef, B)
@@ -604,6 +620,41 @@ function mpc_solve!(bp::BatchedGameProblem, steps::Integer; game_id0::Integer=0,
         pr.x0 = SVector{n}(states[:, g, end])
     end
     return iters, conv, states
+end
+
+"""
+    mpc_solve_log!(bp, steps; game_id0=0, schedule=nothing, disturbance=nothing) -> (newton_iters, converged, states, controls, stats)
+
+The loop of `mpc_solve!` with the closed-loop log (`alg_mpc_solve_log`): `controls` is m x B x steps (the joint control every advance
+applied, player-major), `stats` a B x steps matrix of `AlgGameStats` (every step's solve as `alg_get_stats` reports it).
+`schedule`: as for `mpc_solve!`.  `disturbance`: n x B x rows, finite -- after the advance of the step-th solve the state becomes
+x0 + slice min(step, rows); `states` holds the disturbed states.  It travels as one more schedule kind (`SCHED_DISTURBANCE`): uploaded
+and dropped again with the others.
+"""
+function mpc_solve_log!(bp::BatchedGameProblem, steps::Integer; game_id0::Integer=0, schedule=nothing, disturbance=nothing)
+    sync_options!(bp)
+    B = length(bp.probs); n = bp.probs[1].probsize.n; m = bp.probs[1].probsize.m
+    iters = zeros(Int64, B); conv = zeros(Int64, B)
+    check(ccall((:alg_mpc_totals, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Int32), bp.h, iters, conv, 1))      # reset the totals
+    states = zeros(n, B, steps + 1); controls = zeros(m, B, steps)
+    stats = Matrix{AlgGameStats}(undef, B, steps)
+    up = Dict{Any, Any}()
+    schedule === nothing || merge!(up, schedule)
+    if disturbance !== nothing
+        W = Array{Float64, 3}(disturbance)
+        size(W, 1) == n && size(W, 2) == B && size(W, 3) >= 1 || error("mpc_solve_log!: the disturbance must be $n x $B x rows")
+        up[SCHED_DISTURBANCE] = W
+    end
+    with_schedules(bp, "mpc_solve_log!", up) do
+        check(ccall((:alg_mpc_solve_log, LIB), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{AlgGameStats}),
+                    bp.h, steps, game_id0, states, controls, stats))
+    end
+    check(ccall((:alg_mpc_totals, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Int32), bp.h, iters, conv, 0))
+    pull_results!(bp, stats[:, end])                                # the last solve's iterate, multipliers and statistics
+    for (g, pr) in enumerate(bp.probs)
+        pr.x0 = SVector{n}(states[:, g, end])
+    end
+    return iters, conv, states, controls, stats
 end
 
 # ---- step-wise entry points on a handle (same names as the reference's functions they batch) ------------------------------------

@@ -187,6 +187,22 @@ def c5_scheduled(ids, rows, N=30, seed=100, circle=True, goals=True, backend=Non
     return prob, schedule
 
 
+DISTURBANCE_STREAM = 0x0D157A2B   # keeps the disturbance draws disjoint from the scenario draws of the same id
+
+
+def c5_disturbed(ids, steps, sigma, N=30, seed=100, backend=None, device=0):
+    """The C5 set under plant noise: the 3-player unicycle problem of C5 plus a disturbance for mpc_rollout(problem, steps,
+    disturbance=...).  Returns (problem, disturbance (steps, B, n)): entry e of game g at MPC step t is uniform with mean 0 and standard
+    deviation sigma (in +-sqrt(3) sigma), drawn from the counter-based generator keyed by (global scenario id, t * n + e) -- a pure
+    function of the ids, so the shards of a batch see the numbers of the whole batch."""
+    ids = np.asarray(ids, dtype=np.int64)
+    prob = make_problem("C5", ids, backend=backend, device=device, N=N, seed=seed)
+    n = prob.probsize.n
+    u = counter_uniform((seed + 11) ^ DISTURBANCE_STREAM, ids.astype(np.uint64)[None, :, None],
+                        (np.arange(steps, dtype=np.uint64)[:, None, None] * np.uint64(n) + np.arange(n, dtype=np.uint64)[None, None, :]))
+    return prob, np.ascontiguousarray(float(sigma) * np.sqrt(3.0) * (2.0 * u - 1.0))
+
+
 def make_problem(cfg, ids, backend=None, device=0, devices=None, **kw):
     """cfg in {'C2','C3','C4','C5'} (BASELINE configurations) or 'Q' (quadrotors) -> GameProblem over the scenarios `ids`
     (global scenario ids).  devices=[...]: a sharding.ShardedGameProblem, the batch split contiguously over those devices."""

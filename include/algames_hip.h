@@ -438,7 +438,8 @@ int alg_mpc_solve(alg_handle* h, int32_t steps, int64_t game_id0, double* states
 /* Schedules: values per game AND per MPC step of the numbers that may differ per game, applied inside alg_mpc_solve's single launch --
  * a goal that moves, an obstacle that follows a predicted path -- with the result the step-wise calls give (alg_set_scenario_data /
  * alg_set_lqr with the step's row, alg_newton_solve_async, alg_mpc_advance, once per step).
- *   kind: an ALG_SCEN_* value (len = alg_scenario_data_len(kind)) or ALG_SCHED_LQR_TARGET (len = p*ni + p*mi: xf (p x ni) | uf (p x mi)).
+ *   kind: an ALG_SCEN_* value (len = alg_scenario_data_len(kind)), ALG_SCHED_LQR_TARGET (len = p*ni + p*mi: xf (p x ni) | uf (p x mi)) or
+ *         ALG_SCHED_DISTURBANCE (below).
  *   data: rows x B x len, step-major; NULL drops the kind's schedule.
  *   - in step t (0-based within the call) of alg_mpc_solve game g solves with row min(t, rows - 1) of every scheduled kind: the last row is
  *     held.  The values hold for the whole horizon of that solve (the numbers are constant over a solve, as everywhere).
@@ -459,6 +460,25 @@ int alg_mpc_solve(alg_handle* h, int32_t steps, int64_t game_id0, double* states
 #define ALG_SCHED_LQR_TARGET 100
 int alg_mpc_set_schedule(alg_handle* h, int32_t kind, int32_t rows, const double* data /* rows x B x len, step-major; NULL = drop */);
 int alg_mpc_get_schedule(alg_handle* h, int32_t kind, int32_t* rows /* 0 = none */);
+/* The plant disturbance, one more schedule kind of alg_mpc_set_schedule / alg_mpc_get_schedule with len = n: in step t, after the advance,
+ * game g's state becomes x0 + w[min(t, rows - 1)][g] (one double addition per entry; the last row is held), written to x0 and to x_1 of
+ * pdtraj and trial -- the three places alg_set_x0 writes -- and states[t+1] is the disturbed state.  Step-wise: alg_newton_solve_async,
+ * alg_mpc_advance, read x_1, alg_set_x0(x_1 + w_t).
+ *   - every entry must be finite; rows < 1 with data is refused; on a failure the call returns ALG_ERR_ARG and nothing changes.
+ *   - it needs no per-game data of any other kind and works in both scenario-kernel modes (alg_set_scenario_kernels).
+ *   - any adder (alg_add_*) drops it with all other schedules; alg_set_x0, alg_set_lqr and alg_set_scenario_data keep it.
+ *   - only alg_mpc_solve / alg_mpc_solve_log read it. */
+#define ALG_SCHED_DISTURBANCE 101
+/* alg_mpc_solve with the closed-loop log: the same loop, arguments, errors and totals; alg_mpc_solve(h, s, id, st) is
+ * alg_mpc_solve_log(h, s, id, st, NULL, NULL).
+ *   controls[t][g]: the joint control the advance of step t applies -- u_1 of step t's solution, the m doubles that follow x_2 in the
+ *                   alg_get_traj layout of pdtraj (player-major).
+ *   stats[t][g]:    what alg_get_stats would return after step t's solve (last.t_elap as measured).
+ * The call is synchronous if any of the three output pointers is non-NULL, asynchronous otherwise. */
+int alg_mpc_solve_log(alg_handle* h, int32_t steps, int64_t game_id0,
+                      double* states          /* (steps+1) x B x n, or NULL */,
+                      double* controls        /* steps x B x m, or NULL     */,
+                      alg_game_stats* stats   /* steps x B, or NULL         */);
 
 #ifdef __cplusplus
 }
