@@ -5,6 +5,7 @@ libalgames_hip.so with prefix ``alg_``; the CPU oracle (oracle/, test infrastruc
 same signatures with prefix ``orc_`` and is bound by oracle/oracle.py through this same class.
 """
 import ctypes as C
+import dataclasses
 import numpy as np
 
 ALG_OK = 0
@@ -23,6 +24,8 @@ ALG_SCEN_KERNELS_EXT, ALG_SCEN_KERNELS_BASE = 0, 1
 SCEN_KERNELS = ("ext", "base")
 ALG_SCHED_LQR_TARGET = 100      # alg_mpc_set_schedule: xf (p, ni) | uf (p, mi) per MPC step and game
 ALG_SCHED_DISTURBANCE = 101     # alg_mpc_set_schedule: w (n) per MPC step and game, added to the advanced state
+ALG_PLANT_RK2, ALG_PLANT_RK4 = 0, 1    # alg_mpc_set_plant: the plant's integrator
+PLANT_INTEGRATORS = ("rk2", "rk4")
 SCEN_KINDS = ("collision_radius", "collision_cost", "control_bound", "state_bound", "wall", "circle", "wall3d", "cylinder")
 
 
@@ -41,6 +44,10 @@ class alg_options(C.Structure):
                 ("eps_dyn", C.c_double), ("eps_sta", C.c_double), ("eps_con", C.c_double),
                 ("eps_opt", C.c_double), ("outer_iter", C.c_int32), ("inner_iter", C.c_int32),
                 ("seed", C.c_int64)]
+
+
+class alg_mpc_plant(C.Structure):
+    _fields_ = [("hold", C.c_int32), ("substeps", C.c_int32), ("integrator", C.c_int32), ("reserved", C.c_int32)]
 
 
 class alg_record(C.Structure):
@@ -154,15 +161,48 @@ SIGNATURES = {
     "mpc_set_schedule": (C.c_int, [_P, C.c_int32, C.c_int32, _D]),
     "mpc_get_schedule": (C.c_int, [_P, C.c_int32, _I]),
     "mpc_solve_log": (C.c_int, [_P, C.c_int32, C.c_int64, _D, _D, _P]),
+    "mpc_set_plant": (C.c_int, [_P, C.POINTER(alg_mpc_plant)]),
+    "mpc_get_plant": (C.c_int, [_P, C.POINTER(alg_mpc_plant)]),
+    "mpc_plant_advance": (C.c_int, [_P, C.c_int32]),
 }
 # Entry points a backend may lack (the CPU oracle has no per-game scenario data): bound when present; calling one that is absent
 # raises AlgamesError naming the backend.
 OPTIONAL = frozenset({"scenario_data_len", "set_scenario_data", "get_scenario_data", "set_scenario_kernels", "get_scenario_kernels",
-                      "mpc_set_schedule", "mpc_get_schedule", "mpc_solve_log"})
+                      "mpc_set_schedule", "mpc_get_schedule", "mpc_solve_log", "mpc_set_plant", "mpc_get_plant", "mpc_plant_advance"})
 
 
 class AlgamesError(RuntimeError):
     pass
+
+
+@dataclasses.dataclass(frozen=True)
+class Plant:
+    """The plant of the receding-horizon loop (alg_mpc_set_plant): every solve is followed by `hold` plant knots; knot j holds u_{1+j} of the
+    plan and integrates the state over dt in `substeps` sub-steps with `integrator` -- "rk2", the model's own discrete step, or "rk4", the
+    classical method on the model's continuous dynamics.  Plant() is the loop without a plant: one RK2 step of length dt per solve."""
+    hold: int = 1
+    substeps: int = 1
+    integrator: str = "rk2"
+
+    def __post_init__(self):
+        if isinstance(self.integrator, (int, np.integer)) and not isinstance(self.integrator, bool) and 0 <= int(self.integrator) < len(PLANT_INTEGRATORS):
+            object.__setattr__(self, "integrator", PLANT_INTEGRATORS[int(self.integrator)])
+        if self.integrator not in PLANT_INTEGRATORS:
+            raise ValueError(f"Plant: integrator must be one of {PLANT_INTEGRATORS}, got {self.integrator!r}")
+        for name, hi in (("hold", None), ("substeps", 256)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1 or (hi is not None and v > hi):
+                raise ValueError(f"Plant: {name} must be an integer in 1 ... {hi if hi is not None else 'N - 1'}, got {v!r}")
+            object.__setattr__(self, name, int(v))
+
+    @classmethod
+    def from_options(cls, opts):
+        """The plant the reference's Options ask for: substeps = opts.upsampling, one knot per solve, the model's own step."""
+        return cls(substeps=int(opts.upsampling))
+
+    @property
+    def is_default(self):
+        return self == Plant()
 
 
 def _dptr(a):
@@ -607,18 +647,49 @@ class Batch:
     def mpc_advance(self):
         self.lib.check(self.lib.mpc_advance(self.h))
 
+    # ---- the plant of the fused loop (alg_mpc_set_plant) ------------------------------------
+    def mpc_set_plant(self, plant=None):
+        """Sets the handle's plant (a Plant; None = the default, the loop without a plant).  hold must not exceed N - 1."""
+        if plant is None:
+            self.lib.check(self.lib.mpc_set_plant(self.h, None))
+            return
+        if not isinstance(plant, Plant):
+            raise ValueError(f"mpc_set_plant: expected a Plant or None, got {type(plant).__name__}")
+        if plant.hold > self.N - 1:
+            raise ValueError(f"mpc_set_plant: hold must be in 1 ... N - 1 = {self.N - 1}, got {plant.hold}")
+        c = alg_mpc_plant(plant.hold, plant.substeps, PLANT_INTEGRATORS.index(plant.integrator), 0)
+        self.lib.check(self.lib.mpc_set_plant(self.h, C.byref(c)))
+
+    def mpc_get_plant(self):
+        """The handle's plant (Plant() on a backend without the entry point: such a backend runs the loop without a plant)."""
+        if "mpc_get_plant" in self.lib.absent:
+            return Plant()
+        c = alg_mpc_plant()
+        self.lib.check(self.lib.mpc_get_plant(self.h, C.byref(c)))
+        return Plant(c.hold, c.substeps, PLANT_INTEGRATORS[c.integrator])
+
+    def mpc_plant_advance(self, knot=0):
+        """alg_mpc_plant_advance: one plant knot for every game -- x0 <- Phi(x0, u_{1+knot} of pdtraj) with the handle's plant (asynchronous)."""
+        knot = int(knot)
+        if not 0 <= knot <= self.N - 2:
+            raise ValueError(f"mpc_plant_advance: knot must be in 0 ... N - 2 = {self.N - 2}, got {knot}")
+        self.lib.check(self.lib.mpc_plant_advance(self.h, knot))
+
     def mpc_solve(self, steps, game_id0=0, record_states=False):
-        """The whole receding-horizon loop in one call; returns the states (steps+1, B, n) or None (asynchronous)."""
-        states = np.empty((steps + 1, self.B, self.n)) if record_states else None
+        """The whole receding-horizon loop in one call; returns the states (steps * hold + 1, B, n) -- hold: the handle's plant, 1 without
+        one -- or None (asynchronous)."""
+        states = np.empty((steps * self.mpc_get_plant().hold + 1, self.B, self.n)) if record_states else None
         self.lib.check(self.lib.mpc_solve(self.h, int(steps), int(game_id0), _dptr(states)))
         return states
 
     def mpc_solve_log(self, steps, game_id0=0, states=True, controls=True, stats=True):
-        """alg_mpc_solve_log: the loop of mpc_solve with the closed-loop log.  Returns (states (steps+1, B, n), controls (steps, B, m),
-        stats (steps, B) of game_stats_dtype), None for every part not asked for; asynchronous if none is."""
+        """alg_mpc_solve_log: the loop of mpc_solve with the closed-loop log.  Returns (states (knots+1, B, n), controls (knots, B, m),
+        stats (steps, B) of game_stats_dtype), None for every part not asked for; asynchronous if none is.  knots = steps * hold of the
+        handle's plant (mpc_set_plant), = steps without one."""
         steps = int(steps)
-        st = np.empty((steps + 1, self.B, self.n)) if states else None
-        uc = np.empty((steps, self.B, self.m)) if controls else None
+        knots = steps * self.mpc_get_plant().hold
+        st = np.empty((knots + 1, self.B, self.n)) if states else None
+        uc = np.empty((knots, self.B, self.m)) if controls else None
         gs = np.zeros((steps, self.B), dtype=game_stats_dtype) if stats else None
         self.lib.check(self.lib.mpc_solve_log(self.h, steps, int(game_id0), _dptr(st), _dptr(uc), None if gs is None else gs.ctypes.data_as(_P)))
         return st, uc, gs

@@ -32,6 +32,12 @@ ALG_CFGS_DI1(ALG_DECLARE_SCHED)
 ALG_CFGS_MW(ALG_DECLARE_SCHED_MW)
 ALG_CFGS_MW_SCEN(ALG_DECLARE_SCHED_MW)
 ALG_CFGS_MW_DENSE(ALG_DECLARE_SCHED_MW)
+// the step-wise plant knot (algames_plant.hip)
+ALG_CFGS_BASE(ALG_DECLARE_PLANT)
+ALG_CFGS_BASE_SCEN(ALG_DECLARE_PLANT)
+ALG_CFGS_EXT(ALG_DECLARE_PLANT)
+ALG_CFGS_DENSE(ALG_DECLARE_PLANT)
+ALG_CFGS_DI1(ALG_DECLARE_PLANT)
 
 __global__ void __launch_bounds__(WAVE) k_reset_con(Params pr_arg) {
     CPR pr = kernel_params();
@@ -194,6 +200,7 @@ struct Handle {
         std::vector<int> map;
     } sched[ALG_SCHED_MAX_KINDS];
     Sched dist;                   // the plant disturbance (ALG_SCHED_DISTURBANCE): rows x B x n, no block offsets; rows = 0: none
+    MpcPlant plant{1, 1, ALG_PLANT_RK2, 0};   // alg_mpc_set_plant: independent of constraints and LQR data, nothing but the call itself changes it
     bool keep_sched = false;      // set while alg_set_scenario_data's own switch to the EXT kernels runs (it is no adder: schedules stay)
 };
 
@@ -407,10 +414,11 @@ int launch_mpc_loop_sched(Handle* h, int steps, uint64_t game_id0, double* d_sta
     MpcLoopLog lg; std::memset(&lg, 0, sizeof(lg));
     lg.controls = d_controls; lg.stats = d_stats;
     if (h->dist.rows) { lg.dist = h->dist.d_data; lg.dist_rows = h->dist.rows; }
-    if (nw == 1) { LAUNCH(k_mpc_loop_sched, h->pr, steps, game_id0, d_states, sd, lg); return ALG_OK; }
+    const MpcPlant pl = h->plant;
+    if (nw == 1) { LAUNCH(k_mpc_loop_sched, h->pr, steps, game_id0, d_states, sd, lg, pl); return ALG_OK; }
     const Params& pr = h->pr; bool done = false;
 #define X(M, P, D, E, W) if (!done && nw == (W) && pr.model == (M) && pr.p == (P) && pr.d == (D) && pr.ext == (E)) {                   \
-        hipLaunchKernelGGL((k_mpc_loop_sched<Cfg<M, P, D, E, W>>), dim3(pr.B), dim3(WAVE * (W)), 0, h->stream, h->pr, steps, game_id0, d_states, sd, lg); done = true; }
+        hipLaunchKernelGGL((k_mpc_loop_sched<Cfg<M, P, D, E, W>>), dim3(pr.B), dim3(WAVE * (W)), 0, h->stream, h->pr, steps, game_id0, d_states, sd, lg, pl); done = true; }
     ALG_CFGS_MW(X)
     ALG_CFGS_MW_SCEN(X)
     ALG_CFGS_MW_DENSE(X)
@@ -1344,6 +1352,29 @@ int alg_mpc_advance(alg_handle* h) {
     LAUNCH(k_mpc_advance, H->pr);
     return ALG_OK;
 }
+// The plant of the fused loop and the step-wise form of one of its knots (include/algames_hip.h)
+int alg_mpc_set_plant(alg_handle* h, const alg_mpc_plant* p) {
+    NEED_HANDLE("alg_mpc_set_plant");
+    if (!p) { H->plant = MpcPlant{1, 1, ALG_PLANT_RK2, 0}; return ALG_OK; }
+    if (p->hold < 1 || p->hold > H->pr.N - 1) return fail(ALG_ERR_ARG, "alg_mpc_set_plant: hold must be in 1 ... N - 1");
+    if (p->substeps < 1 || p->substeps > 256) return fail(ALG_ERR_ARG, "alg_mpc_set_plant: substeps must be in 1 ... 256");
+    if (p->integrator != ALG_PLANT_RK2 && p->integrator != ALG_PLANT_RK4) return fail(ALG_ERR_ARG, "alg_mpc_set_plant: integrator must be ALG_PLANT_RK2 or ALG_PLANT_RK4");
+    if (p->reserved != 0) return fail(ALG_ERR_ARG, "alg_mpc_set_plant: reserved must be 0");
+    H->plant = MpcPlant{p->hold, p->substeps, p->integrator, 0};
+    return ALG_OK;
+}
+int alg_mpc_get_plant(alg_handle* h, alg_mpc_plant* p) {
+    if (!h || !p) return fail(ALG_ERR_ARG, "alg_mpc_get_plant: null argument");
+    p->hold = H->plant.hold; p->substeps = H->plant.substeps; p->integrator = H->plant.integrator; p->reserved = 0;
+    return ALG_OK;
+}
+int alg_mpc_plant_advance(alg_handle* h, int32_t knot) {
+    NEED_HANDLE("alg_mpc_plant_advance");
+    if (knot < 0 || knot > H->pr.N - 2) return fail(ALG_ERR_ARG, "alg_mpc_plant_advance: knot must be in 0 ... N - 2");
+    int rc = use_device(H); if (rc) return rc;
+    LAUNCH(k_mpc_plant_advance, H->pr, (int)knot, H->plant);
+    return ALG_OK;
+}
 } // extern "C"
 // The loop of alg_mpc_solve and alg_mpc_solve_log; `who` names the entry point in the error messages
 static int mpc_solve_impl(const char* who, alg_handle* h, int32_t steps, int64_t game_id0, double* states, double* controls, alg_game_stats* stats) {
@@ -1351,8 +1382,11 @@ static int mpc_solve_impl(const char* who, alg_handle* h, int32_t steps, int64_t
     int rc = use_device(H); if (rc) return rc;
     if (!H->x0_set || !H->lqr_set) return fail(ALG_ERR_STATE, std::string(who) + ": x0 / LQR data not set");
     const Params& p = H->pr;
-    // one scratch allocation for all requested outputs: [states | controls | stats], every part 8-byte aligned
-    const size_t b_st = states ? sizeof(double) * (size_t)(steps + 1) * p.B * p.n : 0, b_uc = controls ? sizeof(double) * (size_t)steps * p.B * p.m : 0,
+    // one scratch allocation for all requested outputs: [states | controls | stats], every part 8-byte aligned; under a plant (alg_mpc_set_plant)
+    // states and controls hold one row per plant knot, steps x hold of them
+    const size_t knots = (size_t)steps * (size_t)H->plant.hold;
+    const bool planted = !mpc_plant_is_default(H->plant.hold, H->plant.substeps, H->plant.integrator);
+    const size_t b_st = states ? sizeof(double) * (knots + 1) * p.B * p.n : 0, b_uc = controls ? sizeof(double) * knots * p.B * p.m : 0,
                  b_gs = stats ? sizeof(alg_game_stats) * (size_t)steps * p.B : 0;
     static_assert(sizeof(alg_game_stats) % 8 == 0, "the stats log follows doubles in the scratch");
     if (b_st + b_uc + b_gs && (rc = ensure_scratch(H, b_st + b_uc + b_gs))) return rc;
@@ -1362,8 +1396,8 @@ static int mpc_solve_impl(const char* who, alg_handle* h, int32_t steps, int64_t
     alg_game_stats* const d_stats = stats ? (alg_game_stats*)(d0 + b_st + b_uc) : nullptr;
     bool scheduled = false;
     for (int k = 0; k < ALG_SCHED_MAX_KINDS; k++) scheduled |= H->sched[k].rows > 0;
-    // the sibling kernels are the loop with per-step phases: a schedule, a disturbance or a log takes them
-    if (!scheduled && !H->dist.rows && !controls && !stats) rc = launch_mpc_loop(H, (int)steps, (uint64_t)game_id0, d_states);
+    // the sibling kernels are the loop with per-step phases: a schedule, a disturbance, a log or a plant takes them
+    if (!scheduled && !H->dist.rows && !controls && !stats && !planted) rc = launch_mpc_loop(H, (int)steps, (uint64_t)game_id0, d_states);
     else rc = launch_mpc_loop_sched(H, (int)steps, (uint64_t)game_id0, d_states, d_controls, d_stats);
     if (rc) return rc;
     // the loop leaves the row its last step used in the games' blocks: the host mirror of the scenario blocks follows (what the step-wise

@@ -251,8 +251,8 @@ __global__ void __launch_bounds__(C::NT, mpc_loop_wpe<C>) k_mpc_loop(Params pr_a
 // The receding-horizon loop with a SCHEDULE (alg_mpc_set_schedule): per game and per MPC step values of the numbers that may differ per
 // game -- the kinds of the scenario block and the LQR targets xf / uf.  A sibling of k_mpc_loop, not one more argument of it: k_mpc_loop's
 // source, and with it the binary of every unscheduled loop, stays what it was; the siblings live in translation units of
-// their own (algames_sched.hip) and are launched only while the handle carries a schedule or a disturbance, or the call asks for a log
-// (alg_mpc_solve_log): the sibling is the loop with per-step phases.
+// their own (algames_sched.hip) and are launched only while the handle carries a schedule, a disturbance or a plant (alg_mpc_set_plant), or the
+// call asks for a log (alg_mpc_solve_log): the sibling is the loop with per-step phases.
 // The schedule sits in device memory in compact form, rows x B x len doubles per kind, with a table of len block offsets per kind (the host's
 // scen_map; ALG_SCHED_TO_LQR marks an offset into the game's LQR block, a negative entry is skipped like alg_set_scenario_data skips it).
 // Before every solve the game's wavefronts copy row min(t, rows - 1) of every kind into the game's own blocks with ordinary vector stores.
@@ -267,7 +267,6 @@ struct MpcSched { int nk, pad_; MpcSchedKind k[ALG_SCHED_MAX_KINDS]; };
 // applies (u_1 of pdtraj, the m doubles behind x_2) and the game's alg_game_stats as the solve left them -- and the plant DISTURBANCE
 // w[min(t, rows - 1)][g], added to the advanced state.  A null pointer skips its part.  Descriptors of their own in the kernel-argument segment.
 struct MpcLoopLog { double* controls; alg_game_stats* stats; const double* dist; int dist_rows, pad_; };
-struct MpcLoopSchedArgs { Params pr; int steps; uint64_t game_id0; double* states; MpcSched sd; MpcLoopLog lg; };
 template <class C>
 __device__ __forceinline__ void mpc_apply_schedule(CPR pr, const ALG_AS4 MpcSched& sd, const int g, const int t) {
     const int tid = phase_lane(), nk = sd.nk;
@@ -310,9 +309,140 @@ __device__ __forceinline__ void mpc_disturb(CPR pr, const Game& G, const ALG_AS4
         G.x0w(pr)[tid] = v; G.z(0)[tid] = v; G.z(1)[tid] = v;
     }
 }
+// The PLANT (alg_mpc_set_plant): every solve is followed by `hold` plant knots j = 0 ... hold - 1; knot j holds u_{1+j} of the
+// solve's pdtraj and integrates the state over dt in `substeps` sub-steps of h = dt / substeps, with the model's own RK2 step (the expression
+// mpc_advance evaluates, called with h) or the classical RK4 on the model's continuous dynamics.  {1, 1, RK2} is the loop without a plant.
+struct MpcPlant { int hold, substeps, integrator, pad_; };
+struct MpcLoopSchedArgs { Params pr; int steps; uint64_t game_id0; double* states; MpcSched sd; MpcLoopLog lg; MpcPlant pl; };
+__host__ __device__ inline bool mpc_plant_is_default(int hold, int substeps, int integrator) { return hold == 1 && substeps == 1 && integrator == ALG_PLANT_RK2; }
+// the continuous dynamics of one player on its own entries (the f of model_player_rk3_own / quad_f)
+template <class C>
+__device__ __forceinline__ void plant_f(CPR pr, const double (&s)[C::ni], const double (&ui)[C::mi], double (&o)[C::ni]) {
+    if constexpr (C::QUAD) {
+        quad_f(s, ui, pr.qmass, o);
+    } else if constexpr (C::MODEL == ALG_MODEL_DOUBLE_INTEGRATOR) {
+#pragma unroll
+        for (int j = 0; j < C::D; j++) { o[j] = s[C::D + j]; o[C::D + j] = ui[j]; }
+    } else if constexpr (C::MODEL == ALG_MODEL_BICYCLE) {
+        const BikeGeom g = bike_geom(ui[1], pr.lf, pr.lr);
+        double sn, cs; sincos(g.beta + s[3], &sn, &cs);
+        o[0] = s[2] * cs; o[1] = s[2] * sn; o[2] = ui[0]; o[3] = s[2] * g.sg;
+    } else {
+        double sn, cs; sincos(s[2], &sn, &cs);
+        o[0] = cs * s[3]; o[1] = sn * s[3]; o[2] = ui[0]; o[3] = ui[1];
+    }
+}
+// the model's own discrete step (model_player, quad_rk2) on the player's own entries: the same expressions, entry for entry
+template <class C>
+__device__ __forceinline__ void plant_rk2(CPR pr, const double (&xi)[C::ni], const double (&ui)[C::mi], const double dt, double (&xn)[C::ni]) {
+    if constexpr (C::QUAD) {
+        quad_rk2(xi, ui, pr.qmass, dt, xn);
+    } else if constexpr (C::MODEL == ALG_MODEL_DOUBLE_INTEGRATOR) {
+#pragma unroll
+        for (int j = 0; j < C::D; j++) {
+            const double vm = xi[C::D + j] + (ui[j] * dt) * 0.5;
+            xn[j] = xi[j] + vm * dt;
+            xn[C::D + j] = xi[C::D + j] + ui[j] * dt;
+        }
+    } else if constexpr (C::MODEL == ALG_MODEL_BICYCLE) {
+        const double v = xi[2], psi = xi[3], a = ui[0];
+        const BikeGeom g = bike_geom(ui[1], pr.lf, pr.lr);
+        const double vm = v + (a * dt) * 0.5, psm = psi + (v * g.sg * dt) * 0.5;
+        double s, c; sincos(g.beta + psm, &s, &c);
+        xn[0] = xi[0] + (vm * c) * dt;
+        xn[1] = xi[1] + (vm * s) * dt;
+        xn[2] = v + a * dt;
+        xn[3] = psi + (vm * g.sg) * dt;
+    } else {
+        const double th = xi[2], v = xi[3], om = ui[0], a = ui[1];
+        const double thm = th + (om * dt) * 0.5, vm = v + (a * dt) * 0.5;
+        double s, c;
+        sincos(thm, &s, &c);
+        xn[0] = xi[0] + (c * vm) * dt;
+        xn[1] = xi[1] + (s * vm) * dt;
+        xn[2] = th + om * dt;
+        xn[3] = v + a * dt;
+    }
+}
+// classical RK4: the stage vector, the running sum and the stage state are register arrays with compile-time indices
+template <class C>
+__device__ __forceinline__ void plant_rk4(CPR pr, const double (&xi)[C::ni], const double (&ui)[C::mi], const double h, double (&xn)[C::ni]) {
+    double k[C::ni], acc[C::ni], t[C::ni];
+    plant_f<C>(pr, xi, ui, k);
+#pragma unroll
+    for (int j = 0; j < C::ni; j++) { acc[j] = k[j]; t[j] = xi[j] + (h * 0.5) * k[j]; }
+    plant_f<C>(pr, t, ui, k);
+#pragma unroll
+    for (int j = 0; j < C::ni; j++) { acc[j] = acc[j] + 2.0 * k[j]; t[j] = xi[j] + (h * 0.5) * k[j]; }
+    plant_f<C>(pr, t, ui, k);
+#pragma unroll
+    for (int j = 0; j < C::ni; j++) { acc[j] = acc[j] + 2.0 * k[j]; t[j] = xi[j] + h * k[j]; }
+    plant_f<C>(pr, t, ui, k);
+#pragma unroll
+    for (int j = 0; j < C::ni; j++) xn[j] = xi[j] + (h / 6.0) * (acc[j] + k[j]);
+}
+// One plant knot of one game: x0 <- Phi(x0, u_{1+knot} of pdtraj), written to the three places alg_set_x0 writes; lanes < P own a player, as
+// in mpc_advance.  The totals gain the solve once per solve (knot 0).  `uc` (or null) receives the control held, in the stored order.
+// Serves the fused loop (k_mpc_loop_sched) and alg_mpc_plant_advance (k_mpc_plant_advance): fused equals step-wise bit for bit.
+template <class C>
+__device__ __forceinline__ void mpc_plant_knot(CPR pr, const Game& G, const int knot, const int substeps, const int integrator, double* const uc) {
+    const int lane = phase_lane();
+    const double* const u = G.z(0) + C::n + knot * C::b + C::n;
+    if (uc && lane < C::m) uc[lane] = u[lane];
+    if (lane < C::P) {
+        double xi[C::ni], ui[C::mi], xo[C::ni];
+#pragma unroll
+        for (int j = 0; j < C::ni; j++) xi[j] = G.x0(pr)[lane + j * C::P];
+#pragma unroll
+        for (int j = 0; j < C::mi; j++) ui[j] = u[lane * C::mi + j];
+        const double h = pr.dt / (double)substeps;
+        for (int s = 0; s < substeps; s++) {
+            // (an opaque copy of h per sub-step: products of h and the held control are loop invariants, and hoisted out of the loop they sit in
+            // another block than the additions they feed -- no longer one fused multiply-add as in mpc_advance, i.e. other bits)
+            const double hs = phase_f64(h);
+            if (integrator == ALG_PLANT_RK4) plant_rk4<C>(pr, xi, ui, hs, xo);
+            else plant_rk2<C>(pr, xi, ui, hs, xo);
+#pragma unroll
+            for (int j = 0; j < C::ni; j++) xi[j] = xo[j];
+        }
+#pragma unroll
+        for (int j = 0; j < C::ni; j++) { const int a = lane + j * C::P; G.x0w(pr)[a] = xi[j]; G.z(0)[a] = xi[j]; G.z(1)[a] = xi[j]; }
+    }
+    if (lane == 0 && knot == 0) { G.mpc(pr)[0] += G.st(pr)->newton_iters; G.mpc(pr)[1] += G.st(pr)->converged; }
+}
+// alg_mpc_plant_advance: the step-wise form of one plant knot (one wavefront per game, like every step-wise entry point)
+template <class C>
+__global__ void __launch_bounds__(WAVE) k_mpc_plant_advance(Params pr_arg, int knot, MpcPlant pl) {
+    CPR pr = kernel_params();
+    const int g = blockIdx.x;
+    Game G = game_view(pr, g);
+    mpc_plant_knot<C>(pr, G, knot, pl.substeps, pl.integrator, nullptr);
+}
+// the second phase of a knot in the fused loop: the disturbance row of knot q (one addition on the STORED value, like mpc_disturb) and the
+// state log states[q + 1]
+template <class C>
+__device__ __forceinline__ void mpc_plant_store(CPR pr, const Game& G, const ALG_AS4 MpcLoopLog& lg, double* const states, const int g, const int q) {
+    const int tid = phase_lane();
+    if (tid >= C::n) return;
+    double v = G.x0w(pr)[tid];
+    const double* const w = lg.dist;
+    if (w) {
+        const int rows = lg.dist_rows, row = q < rows ? q : rows - 1;      // the last row is held
+        v = v + as_global(w)[((size_t)row * pr.B + g) * C::n + tid];
+        G.x0w(pr)[tid] = v; G.z(0)[tid] = v; G.z(1)[tid] = v;
+    }
+    if (states) as_global(states)[((size_t)(q + 1) * pr.B + g) * C::n + tid] = v;
+}
+// the statistics of solve t (the part of mpc_log_step that is per solve under a plant too)
+__device__ __forceinline__ void mpc_log_stats(CPR pr, const Game& G, const ALG_AS4 MpcLoopLog& lg, const int g, const int t) {
+    alg_game_stats* const so = lg.stats;
+    constexpr int W = (int)(sizeof(alg_game_stats) / 8);
+    const int tid = phase_lane();
+    if (so && tid < W) reinterpret_cast<unsigned long long*>(as_global(so) + ((size_t)t * pr.B + g))[tid] = reinterpret_cast<const unsigned long long*>(G.st(pr))[tid];
+}
 template <class C>
 __global__ void __launch_bounds__(C::NT, mpc_loop_wpe<C>) k_mpc_loop_sched(Params pr_arg, int steps_arg, uint64_t game_id0_arg, double* states_arg, MpcSched sd_arg,
-                                                                            MpcLoopLog lg_arg) {
+                                                                            MpcLoopLog lg_arg, MpcPlant pl_arg) {
     __shared__ Lds<C> L;
     CPR pr = kernel_params();
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -335,19 +465,38 @@ __global__ void __launch_bounds__(C::NT, mpc_loop_wpe<C>) k_mpc_loop_sched(Param
         mpc_apply_schedule<C>(phase_params(pr), kq().sd, phase_int(g), t);
         __syncthreads();
         const int gq = phase_int(g);
-        newton_solve<C, 0, mpc_loop_launder_v<C>>(pr, G, L, 1, kq().game_id0 + (uint64_t)t * 1000003ull + (uint64_t)gq, t == 0 ? -1 : 1, t == 0 ? -1 : 0);
+        // (the warm start of solve t >= 1 is shifted by the knots the plant held: 1 without a plant)
+        newton_solve<C, 0, mpc_loop_launder_v<C>>(pr, G, L, 1, kq().game_id0 + (uint64_t)t * 1000003ull + (uint64_t)gq, t == 0 ? -1 : kq().pl.hold, t == 0 ? -1 : 0);
         __syncthreads();
-        // the log phase, the advance, the disturbance phase: each behind a barrier, each from the opaque roots like the schedule phase
-        mpc_log_step<C>(phase_params(pr), G.fresh(), kq().lg, phase_int(g), t);
-        __syncthreads();
-        mpc_advance<C>(phase_params(pr), G.fresh());
-        __syncthreads();
-        mpc_disturb<C>(phase_params(pr), G.fresh(), kq().lg, phase_int(g), t);
-        __syncthreads();
-        double* const states = kq().states;
-        const int ln = phase_lane();
-        if (states && ln < C::n) { CPR prs = phase_params(pr); states[((size_t)(t + 1) * prs.B + phase_int(g)) * C::n + ln] = G.fresh().z(0)[ln]; }
-        __syncthreads();
+        if (mpc_plant_is_default(kq().pl.hold, kq().pl.substeps, kq().pl.integrator)) {
+            // the log phase, the advance, the disturbance phase: each behind a barrier, each from the opaque roots like the schedule phase
+            mpc_log_step<C>(phase_params(pr), G.fresh(), kq().lg, phase_int(g), t);
+            __syncthreads();
+            mpc_advance<C>(phase_params(pr), G.fresh());
+            __syncthreads();
+            mpc_disturb<C>(phase_params(pr), G.fresh(), kq().lg, phase_int(g), t);
+            __syncthreads();
+            double* const states = kq().states;
+            const int ln = phase_lane();
+            if (states && ln < C::n) { CPR prs = phase_params(pr); states[((size_t)(t + 1) * prs.B + phase_int(g)) * C::n + ln] = G.fresh().z(0)[ln]; }
+            __syncthreads();
+        } else {
+            // the plant phase: the statistics of the solve, then `hold` knots of two phases each -- [control log | plant step] and
+            // [disturbance | state log] -- each behind a barrier and from the opaque roots; only t and the knot counter live across them
+            mpc_log_stats(phase_params(pr), G.fresh(), kq().lg, phase_int(g), t);
+            for (int j = 0; j < kq().pl.hold; j++) {
+                __syncthreads();
+                {
+                    CPR prk = phase_params(pr);
+                    double* const uc = kq().lg.controls;
+                    const size_t q = (size_t)t * kq().pl.hold + j;
+                    mpc_plant_knot<C>(prk, G.fresh(), j, kq().pl.substeps, kq().pl.integrator, uc ? as_global(uc) + (q * prk.B + phase_int(g)) * C::m : nullptr);
+                }
+                __syncthreads();
+                mpc_plant_store<C>(phase_params(pr), G.fresh(), kq().lg, kq().states, phase_int(g), t * kq().pl.hold + j);
+            }
+            __syncthreads();
+        }
         if (t + 1 >= kq().steps) break;
     }
 }
@@ -514,9 +663,13 @@ __global__ void __launch_bounds__(C::NT, mpc_loop_wpe<C>) k_mpc_loop_sched(Param
 #define ALG_DEFINE_KERNELS(M, P, D, E) ALG_INSTANTIATE_KERNELS(template, M, P, D, E)
 #define ALG_DECLARE_KERNELS(M, P, D, E) ALG_INSTANTIATE_KERNELS(extern template, M, P, D, E)
 // The scheduled receding-horizon loops (k_mpc_loop_sched): one per loop kernel of the lists above, defined in algames_sched.hip
-#define ALG_INSTANTIATE_SCHED(PREFIX, M, P, D, E) PREFIX __global__ void k_mpc_loop_sched<Cfg<M, P, D, E>>(Params, int, uint64_t, double*, MpcSched, MpcLoopLog);
-#define ALG_INSTANTIATE_SCHED_MW(PREFIX, M, P, D, E, W) PREFIX __global__ void k_mpc_loop_sched<Cfg<M, P, D, E, W>>(Params, int, uint64_t, double*, MpcSched, MpcLoopLog);
+#define ALG_INSTANTIATE_SCHED(PREFIX, M, P, D, E) PREFIX __global__ void k_mpc_loop_sched<Cfg<M, P, D, E>>(Params, int, uint64_t, double*, MpcSched, MpcLoopLog, MpcPlant);
+#define ALG_INSTANTIATE_SCHED_MW(PREFIX, M, P, D, E, W) PREFIX __global__ void k_mpc_loop_sched<Cfg<M, P, D, E, W>>(Params, int, uint64_t, double*, MpcSched, MpcLoopLog, MpcPlant);
 #define ALG_DEFINE_SCHED(M, P, D, E) ALG_INSTANTIATE_SCHED(template, M, P, D, E)
 #define ALG_DECLARE_SCHED(M, P, D, E) ALG_INSTANTIATE_SCHED(extern template, M, P, D, E)
 #define ALG_DEFINE_SCHED_MW(M, P, D, E, W) ALG_INSTANTIATE_SCHED_MW(template, M, P, D, E, W)
+// The step-wise plant knot (k_mpc_plant_advance): one per one-wavefront configuration, defined in algames_plant.hip
+#define ALG_INSTANTIATE_PLANT(PREFIX, M, P, D, E) PREFIX __global__ void k_mpc_plant_advance<Cfg<M, P, D, E>>(Params, int, MpcPlant);
+#define ALG_DEFINE_PLANT(M, P, D, E) ALG_INSTANTIATE_PLANT(template, M, P, D, E)
+#define ALG_DECLARE_PLANT(M, P, D, E) ALG_INSTANTIATE_PLANT(extern template, M, P, D, E)
 #define ALG_DECLARE_SCHED_MW(M, P, D, E, W) ALG_INSTANTIATE_SCHED_MW(extern template, M, P, D, E, W)

@@ -9,6 +9,7 @@ Reference: src/Algames.jl:19-165 (exports), src/problem/problem.jl, src/problem/
 src/struct/*.jl, src/dynamics/{double_integrator,unicycle}.jl, src/objective/objective.jl,
 src/constraints/{game_constraints,constraints_methods}.jl.
 """
+import contextlib
 import dataclasses
 import os
 
@@ -16,7 +17,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import (ALG_MODEL_BICYCLE, ALG_MODEL_DOUBLE_INTEGRATOR, ALG_MODEL_QUADROTOR, ALG_MODEL_UNICYCLE, ALG_TRAJ_PD, ALG_TRAJ_TRIAL,
-                   ALG_TRAJ_DELTA, ALG_SCHED_LQR_TARGET, ALG_SCHED_DISTURBANCE, AlgamesError, Batch, CLib)
+                   ALG_TRAJ_DELTA, ALG_SCHED_LQR_TARGET, ALG_SCHED_DISTURBANCE, AlgamesError, Batch, CLib, Plant)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.environ.get("ALGAMES_HIP_LIB", os.path.join(_HERE, "lib", "libalgames_hip.so"))
@@ -1066,56 +1067,82 @@ def _apply_schedule_rows(prob, sched, t):
             b.set_scenario_data(k, a[r])
 
 
-def mpc_solve(prob, steps, record_states=False, fused=True, schedule=None):
+@contextlib.contextmanager
+def _with_plant(b, plant):
+    """the handle's plant for one call: `plant` is set and the previous one restored; None leaves the handle alone.  Yields the plant in force."""
+    if plant is None:
+        yield b.mpc_get_plant()
+        return
+    if not isinstance(plant, Plant):
+        raise ValueError(f"plant: expected a Plant or None, got {type(plant).__name__}")
+    old = b.mpc_get_plant()
+    b.mpc_set_plant(plant)
+    try:
+        yield plant
+    finally:
+        b.mpc_set_plant(old)
+
+
+def mpc_solve(prob, steps, record_states=False, fused=True, schedule=None, plant=None):
     """Runs `steps` receding-horizon solves for every game of the batch.  Returns (newton_iters (B,), converged (B,),
-    states (steps+1, B, n) or None).  fused=True: one launch, every game runs its own loop (alg_mpc_solve); fused=False:
-    one newton_solve! launch + one advance launch per MPC step (the batch waits for its slowest game at every step).
+    states (steps * hold + 1, B, n) or None).  fused=True: one launch, every game runs its own loop (alg_mpc_solve); fused=False:
+    one newton_solve! launch + one advance launch per plant knot (the batch waits for its slowest game at every step).
     No host synchronisation happens inside the loop unless record_states is set.
 
     schedule: {kind: array (rows, B, len)} -- values per MPC step and game of the numbers that may differ per game; kind is a scenario
     kind (Batch.set_scenario_data) or "lqr_target" (xf (p, ni) | uf (p, mi) of every game; the problem needs per-game LQR data).  Step t
     solves with row min(t, rows - 1) of every kind.  fused=True uploads the schedule (Batch.mpc_set_schedule), launches once and drops it
     again; fused=False applies the step's rows through set_scenario_data / set_lqr before each step's solve -- the definition the fused
-    path is held to.  Either way the handle keeps the rows the last step used."""
+    path is held to.  Either way the handle keeps the rows the last step used.
+
+    plant: a Plant -- every solve is followed by plant.hold plant knots, each integrated in plant.substeps sub-steps (see mpc_rollout);
+    set on the handle for the call and restored afterwards.  None: the handle's own plant, by default the loop without one."""
     b = prob.batch
     sched = _mpc_schedule(b, schedule)
-    b.mpc_totals(reset=True)
-    prob._sync_options()
-    if fused:
-        for k, a in sched:
-            b.mpc_set_schedule(k, a)
+    with _with_plant(b, plant) as pl:
+        b.mpc_totals(reset=True)
+        prob._sync_options()
+        if fused:
+            for k, a in sched:
+                b.mpc_set_schedule(k, a)
+            try:
+                states = b.mpc_solve(steps, prob.game_id0, record_states)
+                it, cv = b.mpc_totals()
+            finally:
+                for k, a in sched:
+                    b.mpc_set_schedule(k, None)
+            return it, cv, states
+        shift0, reset0 = prob.opts.shift, prob.opts.dual_reset
+        states = [b.get_x0()] if record_states else None
+        stepwise_plant = plant is not None or not pl.is_default
+
         try:
-            states = b.mpc_solve(steps, prob.game_id0, record_states)
+            for t in range(steps):
+                if t == 1:
+                    prob.opts.shift, prob.opts.dual_reset = pl.hold, False
+                    prob._sync_options()
+                _apply_schedule_rows(prob, sched, t)
+                b.newton_solve_async(init=True, game_id0=prob.game_id0 + t * 1000003)
+                for j in range(pl.hold):
+                    if stepwise_plant:
+                        b.mpc_plant_advance(j)
+                    else:
+                        b.mpc_advance()
+                    if record_states:
+                        states.append(b.get_x0())
             it, cv = b.mpc_totals()
         finally:
-            for k, a in sched:
-                b.mpc_set_schedule(k, None)
-        return it, cv, states
-    shift0, reset0 = prob.opts.shift, prob.opts.dual_reset
-    states = [b.get_x0()] if record_states else None
-
-    try:
-        for t in range(steps):
-            if t == 1:
-                prob.opts.shift, prob.opts.dual_reset = 1, False
-                prob._sync_options()
-            _apply_schedule_rows(prob, sched, t)
-            b.newton_solve_async(init=True, game_id0=prob.game_id0 + t * 1000003)
-            b.mpc_advance()
-            if record_states:
-                states.append(b.get_x0())
-        it, cv = b.mpc_totals()
-    finally:
-        prob.opts.shift, prob.opts.dual_reset = shift0, reset0
-        prob._sync_options()
-    return it, cv, (np.stack(states) if record_states else None)
+            prob.opts.shift, prob.opts.dual_reset = shift0, reset0
+            prob._sync_options()
+        return it, cv, (np.stack(states) if record_states else None)
 
 
 @dataclasses.dataclass
 class MpcRollout:
-    """Closed-loop log of mpc_rollout: states (steps+1, B, n) -- x0 before the loop and after every step, disturbed where a disturbance
-    acts --, controls (steps, B, m) -- the joint control every advance applied, player-major --, stats (steps, B) of game_stats_dtype --
-    every step's solve as get_stats reports it --, and the totals newton_iters (B,), converged (B,)."""
+    """Closed-loop log of mpc_rollout over steps solves and knots = steps * hold plant knots (hold = 1 without a plant): states
+    (knots+1, B, n) -- x0 before the loop and after every knot, disturbed where a disturbance acts --, controls (knots, B, m) -- the joint
+    control every knot held, player-major --, stats (steps, B) of game_stats_dtype -- every step's solve as get_stats reports it --, and the
+    totals newton_iters (B,), converged (B,), which gain every solve once."""
     states: np.ndarray
     controls: np.ndarray
     stats: np.ndarray
@@ -1123,15 +1150,22 @@ class MpcRollout:
     converged: np.ndarray
 
 
-def mpc_rollout(prob, steps, schedule=None, disturbance=None, fused=True):
+def mpc_rollout(prob, steps=None, schedule=None, disturbance=None, fused=True, plant=None):
     """The receding-horizon loop as a closed-loop simulation: mpc_solve's loop with every step observable and a disturbed plant.  Returns
-    an MpcRollout.
+    an MpcRollout.  steps=None takes prob.opts.mpc_horizon.
 
-    schedule: as for mpc_solve.  disturbance: (rows, B, n), finite -- after the advance of step t the state becomes
-    x0 + disturbance[min(t, rows - 1)] (the last row is held); states[t + 1] is the disturbed state.
+    schedule: as for mpc_solve.  disturbance: (rows, B, n), finite -- after plant knot q the state becomes
+    x0 + disturbance[min(q, rows - 1)] (the last row is held); states[q + 1] is the disturbed state.
+    plant: a Plant(hold, substeps, integrator), set on the handle for the call and restored afterwards (None: the handle's own, by default
+    Plant()).  Solve t is followed by the knots q = t * hold + j, j < hold: knot j holds u_{1+j} of the solve's plan and integrates the state
+    over dt in `substeps` sub-steps of the model's own RK2 step ("rk2") or the classical RK4 on its continuous dynamics ("rk4"); the next
+    solve is warm-started with shift = hold.  Without a plant a knot is a step: q = t.
     fused=True: one launch (alg_mpc_solve_log; schedule and disturbance are uploaded and dropped again); fused=False: the definition --
-    per step the schedule rows, newton_solve_async, get_stats and u_1 of get_traj, mpc_advance, x_1 read back, set_x0(x_1 + w_t)."""
+    per step the schedule rows, newton_solve_async, get_stats and the controls of get_traj, then per knot mpc_plant_advance(j) (mpc_advance
+    without a plant), x0 read back, set_x0(x0 + w_q)."""
     b = prob.batch
+    if steps is None:
+        steps = prob.opts.mpc_horizon
     steps = int(steps)
     if steps < 1:
         raise ValueError(f"mpc_rollout: steps must be >= 1, got {steps}")
@@ -1143,41 +1177,49 @@ def mpc_rollout(prob, steps, schedule=None, disturbance=None, fused=True):
             raise ValueError(f"disturbance: expected shape (rows >= 1, {b.B}, {b.n}), got {w.shape}")
         if not np.all(np.isfinite(w)):
             raise ValueError(f"disturbance: every entry must be finite (row {int(np.argwhere(~np.isfinite(w))[0][0])})")
-    b.mpc_totals(reset=True)
-    prob._sync_options()
-    if fused:
-        up = sched + ([(ALG_SCHED_DISTURBANCE, w)] if w is not None else [])
-        done = []
+    with _with_plant(b, plant) as pl:
+        b.mpc_totals(reset=True)
+        prob._sync_options()
+        if fused:
+            up = sched + ([(ALG_SCHED_DISTURBANCE, w)] if w is not None else [])
+            done = []
+            try:
+                for k, a in up:
+                    b.mpc_set_schedule(k, a)
+                    done.append(k)
+                states, controls, stats = b.mpc_solve_log(steps, prob.game_id0)
+                it, cv = b.mpc_totals()
+            finally:
+                for k in done:
+                    b.mpc_set_schedule(k, None)
+            return MpcRollout(states, controls, stats, it, cv)
+        shift0, reset0 = prob.opts.shift, prob.opts.dual_reset
+        n, m = b.n, b.m
+        states, controls, stats = [b.get_x0()], [], []
+        stepwise_plant = plant is not None or not pl.is_default
         try:
-            for k, a in up:
-                b.mpc_set_schedule(k, a)
-                done.append(k)
-            states, controls, stats = b.mpc_solve_log(steps, prob.game_id0)
+            for t in range(steps):
+                if t == 1:
+                    prob.opts.shift, prob.opts.dual_reset = pl.hold, False
+                    prob._sync_options()
+                _apply_schedule_rows(prob, sched, t)
+                b.newton_solve_async(init=True, game_id0=prob.game_id0 + t * 1000003)
+                stats.append(b.get_stats())
+                z = b.get_traj()
+                for j in range(pl.hold):
+                    q = t * pl.hold + j
+                    controls.append(z[:, 2 * n + j * b.b:2 * n + j * b.b + m].copy())
+                    if stepwise_plant:
+                        b.mpc_plant_advance(j)
+                    else:
+                        b.mpc_advance()
+                    x1 = b.get_x0()
+                    if w is not None:
+                        x1 = x1 + w[min(q, w.shape[0] - 1)]
+                        b.set_x0(x1)
+                    states.append(x1)
             it, cv = b.mpc_totals()
         finally:
-            for k in done:
-                b.mpc_set_schedule(k, None)
-        return MpcRollout(states, controls, stats, it, cv)
-    shift0, reset0 = prob.opts.shift, prob.opts.dual_reset
-    n, m = b.n, b.m
-    states, controls, stats = [b.get_x0()], [], []
-    try:
-        for t in range(steps):
-            if t == 1:
-                prob.opts.shift, prob.opts.dual_reset = 1, False
-                prob._sync_options()
-            _apply_schedule_rows(prob, sched, t)
-            b.newton_solve_async(init=True, game_id0=prob.game_id0 + t * 1000003)
-            stats.append(b.get_stats())
-            controls.append(b.get_traj()[:, 2 * n:2 * n + m].copy())
-            b.mpc_advance()
-            x1 = b.get_x0()
-            if w is not None:
-                x1 = x1 + w[min(t, w.shape[0] - 1)]
-                b.set_x0(x1)
-            states.append(x1)
-        it, cv = b.mpc_totals()
-    finally:
-        prob.opts.shift, prob.opts.dual_reset = shift0, reset0
-        prob._sync_options()
-    return MpcRollout(np.stack(states), np.stack(controls), np.stack(stats), it, cv)
+            prob.opts.shift, prob.opts.dual_reset = shift0, reset0
+            prob._sync_options()
+        return MpcRollout(np.stack(states), np.stack(controls), np.stack(stats), it, cv)

@@ -479,6 +479,36 @@ int alg_mpc_solve_log(alg_handle* h, int32_t steps, int64_t game_id0,
                       double* states          /* (steps+1) x B x n, or NULL */,
                       double* controls        /* steps x B x m, or NULL     */,
                       alg_game_stats* stats   /* steps x B, or NULL         */);
+/* The PLANT of the fused loop: the planner runs slower than the plant, and the plant is integrated finer than the planner's
+ * discretisation (the reference's Options carry both knobs, mpc_horizon and upsampling, options.jl:97-102).  Three fields per handle:
+ *   hold (r >= 1), substeps (s >= 1), integrator (ALG_PLANT_RK2 = 0, ALG_PLANT_RK4 = 1).  The default {1, 1, ALG_PLANT_RK2} is the loop above.
+ * MPC step t is solve t, unchanged: game ids game_id0 + t*1000003 + g, schedule rows min(t, rows - 1) of every scenario and target kind
+ * (constant over the solve), stats[t].  The solve is followed by r PLANT KNOTS j = 0 ... r - 1, numbered q = t*r + j:
+ *   1. control:     u = u_{1+j} of solve t's pdtraj, held constant over the knot: in the alg_get_traj layout the m doubles at offset
+ *                   n + j*b + n, b = n + m + n*p (player-major, as stored; the models' joint control vector is component-major).
+ *   2. plant step:  x <- Phi(x, u): s sub-steps of length h = dt / (double)s (one double division).  ALG_PLANT_RK2: each sub-step is the
+ *                   model's own discrete step, the expression alg_mpc_advance evaluates, called with h (s = 1: that expression with dt, bit
+ *                   for bit).  ALG_PLANT_RK4: the classical four-stage method on the model's continuous dynamics, per player; the handle's
+ *                   bicycle lengths and quadrotor mass apply.
+ *   3. disturbance: if the handle carries one, x <- x + w[min(q, rows - 1)][g], one double addition per entry on the stored value.
+ *   4. log:         controls[q][g] = u, states[q + 1][g] = x.
+ * After the last knot x is the game's x0 in the three places alg_set_x0 writes; solve t + 1 runs with shift = r and dual_reset = false.
+ * The totals gain the solve's newton_iters and converged once per solve.  Output sizes of alg_mpc_solve / alg_mpc_solve_log under a plant:
+ * states (steps*r + 1) x B x n, controls steps*r x B x m, stats steps x B.
+ * alg_mpc_set_plant: 1 <= hold <= N - 1, 1 <= substeps <= 256, integrator 0 or 1, reserved == 0; otherwise ALG_ERR_ARG and nothing changes.
+ *   p = NULL restores the default.  The setting is independent of constraints and LQR data: adders, alg_set_options, alg_set_x0, alg_set_lqr,
+ *   alg_set_scenario_data and schedules keep it.
+ * alg_mpc_plant_advance(h, j): the step-wise form of one plant knot (asynchronous): step 2 for every game from the handle's current x0 and
+ *   u_{1+j} of pdtraj, written to x0 and to x_1 of pdtraj and trial; the totals gain the solve only for j == 0; j outside 0 ... N - 2 is
+ *   ALG_ERR_ARG.  With the default plant and j = 0 it is alg_mpc_advance, bit for bit.  The step-wise definition of the loop, per solve:
+ *   the schedule rows; shift = r and dual_reset = 0 from solve 1 on; alg_newton_solve_async; alg_get_stats and the controls from
+ *   alg_get_traj; for j < r: alg_mpc_plant_advance(j), read x0, alg_set_x0(x0 + w_q) if disturbed. */
+#define ALG_PLANT_RK2 0
+#define ALG_PLANT_RK4 1
+typedef struct alg_mpc_plant { int32_t hold, substeps, integrator, reserved; } alg_mpc_plant;
+int alg_mpc_set_plant(alg_handle* h, const alg_mpc_plant* p /* NULL = default */);
+int alg_mpc_get_plant(alg_handle* h, alg_mpc_plant* p);
+int alg_mpc_plant_advance(alg_handle* h, int32_t knot);
 
 #ifdef __cplusplus
 }
