@@ -13,36 +13,63 @@
 // every kernel instantiation lives in its own translation unit: the base configurations in algames_base.hip (compiled once per
 // entry; algames_base_scen.hip / algames_mw_scen.hip: their twins that read the game's scenario block), the EXT instantiations in
 // algames_ext_*.hip, the team kernels in algames_mw.hip, the dense-direction ones in theirs, the scheduled receding-horizon loops in algames_sched.hip
-ALG_CFGS_BASE(ALG_DECLARE_KERNELS)
-ALG_CFGS_BASE_SCEN(ALG_DECLARE_KERNELS)
-ALG_CFGS_MW_SCEN(ALG_DECLARE_MW)
-ALG_CFGS_HANDOFF_SCEN(ALG_DECLARE_HO)
-ALG_CFGS_EXT(ALG_DECLARE_KERNELS)
-ALG_CFGS_DENSE(ALG_DECLARE_KERNELS)
-ALG_CFGS_DI1(ALG_DECLARE_KERNELS)
-ALG_CFGS_MW(ALG_DECLARE_MW)
-ALG_CFGS_MW_DENSE(ALG_DECLARE_MW)
+// (a one-wavefront configuration has its kernels, its scheduled loop and its plant knot, a team its kernels and its scheduled loop)
+#define ALG_DECLARE_ONE_(M, P, D, E) ALG_DECLARE_KERNELS(M, P, D, E) ALG_DECLARE_SCHED(M, P, D, E) ALG_DECLARE_PLANT(M, P, D, E)
+#define ALG_DECLARE_TEAM_(M, P, D, E, W) ALG_DECLARE_MW(M, P, D, E, W) ALG_DECLARE_SCHED_MW(M, P, D, E, W)
+ALG_CFGS_BASE(ALG_DECLARE_ONE_)
+ALG_CFGS_BASE_SCEN(ALG_DECLARE_ONE_)
+ALG_CFGS_EXT(ALG_DECLARE_ONE_)
+ALG_CFGS_DENSE(ALG_DECLARE_ONE_)
+ALG_CFGS_DI1(ALG_DECLARE_ONE_)
+ALG_CFGS_MW(ALG_DECLARE_TEAM_)
+ALG_CFGS_MW_SCEN(ALG_DECLARE_TEAM_)
+ALG_CFGS_MW_DENSE(ALG_DECLARE_TEAM_)
 ALG_CFGS_HANDOFF(ALG_DECLARE_HO)
-// the scheduled receding-horizon loops (algames_sched.hip)
-ALG_CFGS_BASE(ALG_DECLARE_SCHED)
-ALG_CFGS_BASE_SCEN(ALG_DECLARE_SCHED)
-ALG_CFGS_EXT(ALG_DECLARE_SCHED)
-ALG_CFGS_DENSE(ALG_DECLARE_SCHED)
-ALG_CFGS_DI1(ALG_DECLARE_SCHED)
-ALG_CFGS_MW(ALG_DECLARE_SCHED_MW)
-ALG_CFGS_MW_SCEN(ALG_DECLARE_SCHED_MW)
-ALG_CFGS_MW_DENSE(ALG_DECLARE_SCHED_MW)
-// the step-wise plant knot (algames_plant.hip)
-ALG_CFGS_BASE(ALG_DECLARE_PLANT)
-ALG_CFGS_BASE_SCEN(ALG_DECLARE_PLANT)
-ALG_CFGS_EXT(ALG_DECLARE_PLANT)
-ALG_CFGS_DENSE(ALG_DECLARE_PLANT)
-ALG_CFGS_DI1(ALG_DECLARE_PLANT)
+ALG_CFGS_HANDOFF_SCEN(ALG_DECLARE_HO)
 
 __global__ void __launch_bounds__(WAVE) k_reset_con(Params pr_arg) {
     CPR pr = kernel_params();
     Game G = game_view(pr, blockIdx.x);
     reset_con(pr, G);
+}
+
+// Per-knot violation profiles at pdtraj (violations.jl:5-26, 41-67, 86-110, 140-170): the .vio vectors of dynamics_violation,
+// control_violation, state_violation, optimality_violation, from the residual vector (vertical order) and the constraint values a
+// MODE-2 assemble pass (k_residual) has just left in the game's arena.  One wavefront per game, lane = knot; out: [dyn (N-1) | con (N-1) |
+// sta (N) | opt (N)] per game.  Model-independent: only the problem sizes enter.
+__global__ void __launch_bounds__(WAVE) k_vio_profile(Params pr_arg, double* out) {
+    CPR pr = kernel_params();
+    const int g = blockIdx.x, N = pr.N, n = pr.n, m = pr.m, P = pr.p, mi = pr.mi, K = N - 1;
+    Game G = game_view(pr, g);
+    const double* res = G.res(pr); const double* vals = G.vals(pr);
+    double* o = out + (size_t)g * (4 * N - 2);
+    auto pos = [](double c) { return (isfinite(c) && c > 0.0) ? c : 0.0; };
+    for (int j = threadIdx.x; j < N; j += WAVE) {
+        double vopt = 0.0, vsta = 0.0;
+        if (j < K) {
+            double vdyn = 0.0, vcon = 0.0;
+            for (int a = 0; a < n; a++) vdyn = fmax(vdyn, fabs(res[P * K * (n + mi) + j * n + a]));
+            if (pr.has_ctl) for (int r = 0; r < 2 * m; r++) vcon = fmax(vcon, pos(vals[pr.col_len + j * 2 * m + r]));
+            o[j] = vdyn; o[K + j] = vcon;
+            for (int i = 0; i < P; i++) for (int c = 0; c < mi; c++) vopt = fmax(vopt, fabs(res[i * K * (n + mi) + j * (n + mi) + n + c]));      // opt_i,u_{i,k}, knot j + 1
+        }
+        if (j >= 1) {
+            const int k = j - 1;                                                                                                             // step whose x_{k+1} is knot j + 1
+            for (int i = 0; i < P; i++) for (int a = 0; a < n; a++) vopt = fmax(vopt, fabs(res[i * K * (n + mi) + k * (n + mi) + a]));     // opt_i,x, knot j + 1
+            if (pr.has_colavoid) for (int q = 0; q < P * (P - 1); q++) vsta = fmax(vsta, pos(vals[q * K + k]));
+            int e0 = pr.col_len + pr.ctl_len;
+            if (pr.sb_len)   { for (int i = 0; i < P; i++) for (int r = 0; r < 2 * n; r++) vsta = fmax(vsta, pos(vals[e0 + (i * K + k) * 2 * n + r])); }
+            e0 += pr.sb_len;
+            if (pr.wall_len) { for (int i = 0; i < P; i++) for (int w = 0; w < pr.nwall; w++) vsta = fmax(vsta, pos(vals[e0 + (i * K + k) * pr.nwall + w])); }
+            e0 += pr.wall_len;
+            if (pr.circ_len) { for (int i = 0; i < P; i++) for (int w = 0; w < pr.ncirc; w++) vsta = fmax(vsta, pos(vals[e0 + (i * K + k) * pr.ncirc + w])); }
+            e0 += pr.circ_len;
+            if (pr.wall3_len) { for (int i = 0; i < P; i++) for (int w = 0; w < pr.nwall3; w++) vsta = fmax(vsta, pos(vals[e0 + (i * K + k) * pr.nwall3 + w])); }
+            e0 += pr.wall3_len;
+            if (pr.cyl_len)  { for (int i = 0; i < P; i++) for (int w = 0; w < pr.ncyl; w++) vsta = fmax(vsta, pos(vals[e0 + (i * K + k) * pr.ncyl + w])); }
+        }
+        o[2 * K + j] = vsta; o[2 * K + N + j] = vopt;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -136,19 +163,42 @@ void recount_con(Params& p) {
     p.con_len = p.col_len + p.ctl_len + p.sb_len + p.wall_len + p.circ_len + p.wall3_len + p.cyl_len;
 }
 
-// supported template instantiations: ALG_CFGS_BASE / ALG_CFGS_EXT (algames_kernels.hpp).  Params::ext: 0 = base kernels, 1 = EXT kernels,
-// 2 = base layout (constraint rows, multipliers: everything recount_con / alloc_con derive is that of 0) with per-game scenario blocks
-// uploaded: the Cfg::SCEN twins of the base kernels (alg_set_scenario_kernels)
-bool cfg_supported(const Params& p, int ext) {
-#define X(M, P, D, E) if (p.model == (M) && p.p == (P) && p.d == (D) && ext == (E)) return true;
-    ALG_CFGS_BASE(X)
-    ALG_CFGS_BASE_SCEN(X)
-    ALG_CFGS_EXT(X)
-    ALG_CFGS_DENSE(X)
-    ALG_CFGS_DI1(X)
+// The dispatchers: one per family of instantiation lists (algames_kernels.hpp), the only places that match a handle against them.  Each hands
+// the matching entry to `f` as a Cfg value (a kernel template is named from it: kernel<decltype(cfg)>), so whatever alg_create accepts has its
+// launch case.  Params::ext: 0 = base kernels, 1 = EXT kernels, 2 = base layout (constraint rows, multipliers: everything recount_con /
+// alloc_con derive is that of 0) with per-game scenario blocks uploaded: the Cfg::SCEN twins of the base kernels (alg_set_scenario_kernels).
+// One-wavefront kernels: f(Cfg<M, P, D, E>{}) for the entry (model, p, d, ext); false = none compiled.
+template <class F>
+bool dispatch_cfg(const Params& p, int ext, F&& f) {
+#define X(M, P, D, E) if (p.model == (M) && p.p == (P) && p.d == (D) && ext == (E)) { f(Cfg<M, P, D, E>{}); return true; }
+    ALG_CFGS_BASE(X) ALG_CFGS_BASE_SCEN(X) ALG_CFGS_EXT(X) ALG_CFGS_DENSE(X) ALG_CFGS_DI1(X)
 #undef X
     return false;
 }
+// Team kernels: f(Cfg<M, P, D, E, W>{}, dense) for every width W compiled for the handle's (model, p, d, ext) -- nw > 0: for that width
+// only, which the lists hold once; dense = the entry is one of ALG_CFGS_MW_DENSE.  Returns the number of entries handed over.
+template <class F>
+int dispatch_team(const Params& p, int nw, F&& f) {
+    int hits = 0;
+#define TEAM_CASE_(M, P, D, E, W, DENSE) if (p.model == (M) && p.p == (P) && p.d == (D) && p.ext == (E) && (nw == 0 || (nw == (W) && !hits))) { f(Cfg<M, P, D, E, W>{}, DENSE); hits++; }
+#define X(M, P, D, E, W) TEAM_CASE_(M, P, D, E, W, false)
+    ALG_CFGS_MW(X) ALG_CFGS_MW_SCEN(X)
+#undef X
+#define X(M, P, D, E, W) TEAM_CASE_(M, P, D, E, W, true)
+    ALG_CFGS_MW_DENSE(X)
+#undef X
+#undef TEAM_CASE_
+    return hits;
+}
+// Hand-off pairs: f(the budgeted one-wavefront configuration, the team configuration that resumes its parked games)
+template <class F>
+bool dispatch_handoff(const Params& p, F&& f) {
+#define X(M, P, D, E, W) if (p.model == (M) && p.p == (P) && p.d == (D) && p.ext == (E)) { f(Cfg<M, P, D, E>{}, Cfg<M, P, D, E, W, 0>{}); return true; }
+    ALG_CFGS_HANDOFF(X) ALG_CFGS_HANDOFF_SCEN(X)
+#undef X
+    return false;
+}
+bool cfg_supported(const Params& p, int ext) { return dispatch_cfg(p, ext, [](auto) {}); }
 
 int pad16(int x) { return (x + 15) & ~15; }        // per-game segments start on 128-byte lines
 
@@ -238,24 +288,16 @@ int launch_check(const char* what) {
 
 #define H ((Handle*)h)
 #define LAUNCH(kernel, ...) LAUNCH_GRID(H->pr.B, kernel, __VA_ARGS__)
-// (the cases are generated from the instantiation lists of algames_kernels.hpp -- the lists cfg_supported() consults -- so a configuration that
-// alg_create accepts always has its launch case)
+// (macros only because a kernel template can be named through nothing else: the choice itself is dispatch_cfg's)
 #define LAUNCH_GRID(nblocks, kernel, ...)                                                       \
     do {                                                                                        \
-        const Params& pr_ = H->pr;                                                              \
         const int grid_ = (nblocks);                                                            \
-        bool done_ = false;                                                                     \
-        auto launch_ = [&](auto cfg_) {                                                         \
-            hipLaunchKernelGGL((kernel<decltype(cfg_)>), dim3(grid_), dim3(WAVE), 0, H->stream, __VA_ARGS__); \
-            done_ = true;                                                                       \
-        };                                                                                      \
-        ALG_CFGS_BASE(LAUNCH_CASE_) ALG_CFGS_BASE_SCEN(LAUNCH_CASE_) ALG_CFGS_EXT(LAUNCH_CASE_) ALG_CFGS_DENSE(LAUNCH_CASE_) ALG_CFGS_DI1(LAUNCH_CASE_) \
-        if (!done_) return fail(ALG_ERR_ARG, "unsupported (model, p, d) configuration");        \
+        if (!dispatch_cfg(H->pr, H->pr.ext, [&](auto cfg_) {                                    \
+                hipLaunchKernelGGL((kernel<decltype(cfg_)>), dim3(grid_), dim3(WAVE), 0, H->stream, __VA_ARGS__); })) \
+            return fail(ALG_ERR_ARG, "unsupported (model, p, d) configuration");                \
         int rc_ = launch_check(#kernel);                                                        \
         if (rc_ != ALG_OK) return rc_;                                                          \
     } while (0)
-#define LAUNCH_CASE_(M, P, D, E)                                                                \
-    if (!done_ && pr_.model == (M) && pr_.p == (P) && pr_.d == (D) && pr_.ext == (E)) launch_(Cfg<M, P, D, E>{});
 
 void dfree(Handle* h, void* q) {
     for (size_t i = 0; i < h->allocs.size(); i++)
@@ -343,67 +385,55 @@ int ensure_scratch(Handle* hd, size_t bytes) {
 // the batch is so small that B x NW wavefronts still fit the device at two wavefronts per SIMD (1024 SIMDs on MI355X).
 int team_width(const Handle* hd) {
     const Params& p = hd->pr;
-    int best = 1;
-#define X(M, P, D, E, W) if (p.model == (M) && p.p == (P) && p.d == (D) && p.ext == (E)) {                         \
-        if (hd->waves_per_game == (W)) return (W);                                                                    \
-        if (hd->waves_per_game == 0 && (long long)p.B * (W) <= 2048 && (W) > best) best = (W); }
-    ALG_CFGS_MW(X)
-    ALG_CFGS_MW_SCEN(X)
-#undef X
-#define X(M, P, D, E, W) if (p.model == (M) && p.p == (P) && p.d == (D) && p.ext == (E)) {                         \
-        if (hd->waves_per_game == (W)) return (W);                                                                    \
-        if (hd->waves_per_game == 0 && (lds_bound || (long long)p.B * (W) <= 2048) && (W) > best) best = (W); }
+    const int want = hd->waves_per_game;
     // dense direction: once the value matrices alone take more than 16 KB of LDS per game, fewer than one wavefront per SIMD is
     // resident at any batch size and the team of four wins everywhere (measured: quadrotor p = 3 1.7x, p = 4 2.1x at 1024-2048
     // games; p = 2 -- 9.6 KB -- loses 27 % at 4096 games and gains 56 % at 256)
     const bool lds_bound = (long long)p.p * p.n * (p.n + 1) * 8 > 16384;
-    ALG_CFGS_MW_DENSE(X)
-#undef X
-    return hd->waves_per_game > 1 ? -1 : best;
+    int best = 1; bool exact = false;
+    dispatch_team(p, 0, [&](auto cfg, bool dense) {
+        constexpr int W = decltype(cfg)::NW;
+        if (want == W) exact = true;
+        if (want == 0 && ((dense && lds_bound) || (long long)p.B * W <= 2048) && W > best) best = W;
+    });
+    return want > 1 ? (exact ? want : -1) : best;
+}
+const char* const NO_TEAM_WIDTH = "alg_set_waves_per_game: no team kernel of that width is compiled for this configuration";
+// Launch of a fused kernel at the handle's width: `one()` launches the one-wavefront form (a LAUNCH) and returns its code, `team(cfg)`
+// the team kernel of configuration cfg.  A team launch that found no kernel is an error (team_width rules it out).
+template <class One, class Team>
+int launch_fused(Handle* h, const char* what, One&& one, Team&& team) {
+    const int nw = team_width(h);
+    if (nw < 0) return fail(ALG_ERR_ARG, NO_TEAM_WIDTH);
+    if (nw == 1) return one();
+    if (!dispatch_team(h->pr, nw, [&](auto cfg, bool) { team(cfg); })) return fail(ALG_ERR_ARG, std::string(what) + ": nothing launched");
+    return launch_check(what);
 }
 int launch_newton_solve(Handle* h, int init, uint64_t game_id0) {
-    const int nw = team_width(h);
-    if (nw < 0) return fail(ALG_ERR_ARG, "alg_set_waves_per_game: no team kernel of that width is compiled for this configuration");
-    if (nw == 1 && h->handoff > 0 && h->d_ho) {
+    const Params& pr = h->pr;
+    return launch_fused(h, "k_newton_solve (team)", [&]() -> int {
         // straggler hand-off: the budgeted one-wavefront solve parks the games that exceed the budget, the team kernel resumes them
         // (the second launch covers the batch: its blocks past the queue's count leave at once -- no host round trip in between)
-        const Params& pr = h->pr; bool done = false;
-        HIPCHK(hipMemsetAsync(h->d_ho, 0, sizeof(int), h->stream));
-#define X(M, P, D, E, W) if (!done && pr.model == (M) && pr.p == (P) && pr.d == (D) && pr.ext == (E)) {                                \
-        hipLaunchKernelGGL((k_newton_solve_ho<Cfg<M, P, D, E>>), dim3(pr.B), dim3(WAVE), 0, h->stream, h->pr, init, game_id0, h->handoff);  \
-        hipLaunchKernelGGL((k_newton_resume<Cfg<M, P, D, E, W, 0>>), dim3(pr.B), dim3(WAVE * (W)), 0, h->stream, h->pr); done = true; }
-        ALG_CFGS_HANDOFF(X)
-        ALG_CFGS_HANDOFF_SCEN(X)
-#undef X
-        if (done) return launch_check("k_newton_solve_ho / k_newton_resume");
-    }
-    if (nw == 1) { LAUNCH(k_newton_solve, h->pr, init, game_id0); return ALG_OK; }
-    const Params& pr = h->pr; bool done = false;
-#define X(M, P, D, E, W) if (!done && nw == (W) && pr.model == (M) && pr.p == (P) && pr.d == (D) && pr.ext == (E)) {                   \
-        hipLaunchKernelGGL((k_newton_solve<Cfg<M, P, D, E, W>>), dim3(pr.B), dim3(WAVE * (W)), 0, h->stream, h->pr, init, game_id0); done = true; }
-    ALG_CFGS_MW(X)
-    ALG_CFGS_MW_SCEN(X)
-    ALG_CFGS_MW_DENSE(X)
-#undef X
-    return launch_check("k_newton_solve (team)");
+        if (h->handoff > 0 && h->d_ho) {
+            HIPCHK(hipMemsetAsync(h->d_ho, 0, sizeof(int), h->stream));
+            if (dispatch_handoff(pr, [&](auto one, auto team) {
+                    hipLaunchKernelGGL((k_newton_solve_ho<decltype(one)>), dim3(pr.B), dim3(WAVE), 0, h->stream, h->pr, init, game_id0, h->handoff);
+                    hipLaunchKernelGGL((k_newton_resume<decltype(team)>), dim3(pr.B), dim3(WAVE * decltype(team)::NW), 0, h->stream, h->pr); }))
+                return launch_check("k_newton_solve_ho / k_newton_resume");
+        }
+        LAUNCH(k_newton_solve, h->pr, init, game_id0); return ALG_OK;
+    }, [&](auto cfg) {
+        hipLaunchKernelGGL((k_newton_solve<decltype(cfg)>), dim3(pr.B), dim3(WAVE * decltype(cfg)::NW), 0, h->stream, h->pr, init, game_id0);
+    });
 }
 int launch_mpc_loop(Handle* h, int steps, uint64_t game_id0, double* d_states) {
-    const int nw = team_width(h);
-    if (nw < 0) return fail(ALG_ERR_ARG, "alg_set_waves_per_game: no team kernel of that width is compiled for this configuration");
-    if (nw == 1) { LAUNCH(k_mpc_loop, h->pr, steps, game_id0, d_states); return ALG_OK; }
-    const Params& pr = h->pr; bool done = false;
-#define X(M, P, D, E, W) if (!done && nw == (W) && pr.model == (M) && pr.p == (P) && pr.d == (D) && pr.ext == (E)) {                   \
-        hipLaunchKernelGGL((k_mpc_loop<Cfg<M, P, D, E, W>>), dim3(pr.B), dim3(WAVE * (W)), 0, h->stream, h->pr, steps, game_id0, d_states); done = true; }
-    ALG_CFGS_MW(X)
-    ALG_CFGS_MW_SCEN(X)
-    ALG_CFGS_MW_DENSE(X)
-#undef X
-    return launch_check("k_mpc_loop (team)");
+    const Params& pr = h->pr;
+    return launch_fused(h, "k_mpc_loop (team)", [&]() -> int { LAUNCH(k_mpc_loop, h->pr, steps, game_id0, d_states); return ALG_OK; }, [&](auto cfg) {
+        hipLaunchKernelGGL((k_mpc_loop<decltype(cfg)>), dim3(pr.B), dim3(WAVE * decltype(cfg)::NW), 0, h->stream, h->pr, steps, game_id0, d_states);
+    });
 }
 // ... with the handle's schedules (alg_mpc_set_schedule): the sibling kernels, same shapes
 int launch_mpc_loop_sched(Handle* h, int steps, uint64_t game_id0, double* d_states, double* d_controls, alg_game_stats* d_stats) {
-    const int nw = team_width(h);
-    if (nw < 0) return fail(ALG_ERR_ARG, "alg_set_waves_per_game: no team kernel of that width is compiled for this configuration");
     MpcSched sd; std::memset(&sd, 0, sizeof(sd));
     for (int k = 0; k < ALG_SCHED_MAX_KINDS; k++) {
         const Handle::Sched& sc = h->sched[k];
@@ -415,15 +445,10 @@ int launch_mpc_loop_sched(Handle* h, int steps, uint64_t game_id0, double* d_sta
     lg.controls = d_controls; lg.stats = d_stats;
     if (h->dist.rows) { lg.dist = h->dist.d_data; lg.dist_rows = h->dist.rows; }
     const MpcPlant pl = h->plant;
-    if (nw == 1) { LAUNCH(k_mpc_loop_sched, h->pr, steps, game_id0, d_states, sd, lg, pl); return ALG_OK; }
-    const Params& pr = h->pr; bool done = false;
-#define X(M, P, D, E, W) if (!done && nw == (W) && pr.model == (M) && pr.p == (P) && pr.d == (D) && pr.ext == (E)) {                   \
-        hipLaunchKernelGGL((k_mpc_loop_sched<Cfg<M, P, D, E, W>>), dim3(pr.B), dim3(WAVE * (W)), 0, h->stream, h->pr, steps, game_id0, d_states, sd, lg, pl); done = true; }
-    ALG_CFGS_MW(X)
-    ALG_CFGS_MW_SCEN(X)
-    ALG_CFGS_MW_DENSE(X)
-#undef X
-    return launch_check("k_mpc_loop_sched (team)");
+    const Params& pr = h->pr;
+    return launch_fused(h, "k_mpc_loop_sched (team)", [&]() -> int { LAUNCH(k_mpc_loop_sched, h->pr, steps, game_id0, d_states, sd, lg, pl); return ALG_OK; }, [&](auto cfg) {
+        hipLaunchKernelGGL((k_mpc_loop_sched<decltype(cfg)>), dim3(pr.B), dim3(WAVE * decltype(cfg)::NW), 0, h->stream, h->pr, steps, game_id0, d_states, sd, lg, pl);
+    });
 }
 
 int alloc_all(Handle* hd) {
@@ -449,46 +474,331 @@ int alloc_all(Handle* hd) {
 
 int sync(Handle* h) { HIPCHK(hipStreamSynchronize(h->stream)); return ALG_OK; }
 
-} // namespace
-
-// Per-knot violation profiles at pdtraj (violations.jl:5-26, 41-67, 86-110, 140-170): the .vio vectors of dynamics_violation,
-// control_violation, state_violation, optimality_violation, from the residual vector (vertical order) and the constraint values a
-// MODE-2 assemble pass (k_residual) has just left in the game's arena.  One wavefront per game, lane = knot; out: [dyn (N-1) | con (N-1) |
-// sta (N) | opt (N)] per game.  Model-independent: only the problem sizes enter.
-__global__ void __launch_bounds__(WAVE) k_vio_profile(Params pr_arg, double* out) {
-    CPR pr = kernel_params();
-    const int g = blockIdx.x, N = pr.N, n = pr.n, m = pr.m, P = pr.p, mi = pr.mi, K = N - 1;
-    Game G = game_view(pr, g);
-    const double* res = G.res(pr); const double* vals = G.vals(pr);
-    double* o = out + (size_t)g * (4 * N - 2);
-    auto pos = [](double c) { return (isfinite(c) && c > 0.0) ? c : 0.0; };
-    for (int j = threadIdx.x; j < N; j += WAVE) {
-        double vopt = 0.0, vsta = 0.0;
-        if (j < K) {
-            double vdyn = 0.0, vcon = 0.0;
-            for (int a = 0; a < n; a++) vdyn = fmax(vdyn, fabs(res[P * K * (n + mi) + j * n + a]));
-            if (pr.has_ctl) for (int r = 0; r < 2 * m; r++) vcon = fmax(vcon, pos(vals[pr.col_len + j * 2 * m + r]));
-            o[j] = vdyn; o[K + j] = vcon;
-            for (int i = 0; i < P; i++) for (int c = 0; c < mi; c++) vopt = fmax(vopt, fabs(res[i * K * (n + mi) + j * (n + mi) + n + c]));      // opt_i,u_{i,k}, knot j + 1
+// the vector form of the adders: every ordered pair (i, j), radius r_i + r_j (constraints_methods.jl:21-33)
+void set_all_pairs(Params& p, const double* radius) {
+    for (int i = 0; i < MAXP; i++) {
+        p.ca_mask[i] = 0u;
+        for (int j = 0; j < MAXP; j++) {
+            p.ca_pair_r[i * MAXP + j] = 0.0;
+            if (i < p.p && j < p.p && i != j) { p.ca_pair_r[i * MAXP + j] = radius[i] + radius[j]; p.ca_mask[i] |= 1u << j; }
         }
-        if (j >= 1) {
-            const int k = j - 1;                                                                                                             // step whose x_{k+1} is knot j + 1
-            for (int i = 0; i < P; i++) for (int a = 0; a < n; a++) vopt = fmax(vopt, fabs(res[i * K * (n + mi) + k * (n + mi) + a]));     // opt_i,x, knot j + 1
-            if (pr.has_colavoid) for (int q = 0; q < P * (P - 1); q++) vsta = fmax(vsta, pos(vals[q * K + k]));
-            int e0 = pr.col_len + pr.ctl_len;
-            if (pr.sb_len)   { for (int i = 0; i < P; i++) for (int r = 0; r < 2 * n; r++) vsta = fmax(vsta, pos(vals[e0 + (i * K + k) * 2 * n + r])); }
-            e0 += pr.sb_len;
-            if (pr.wall_len) { for (int i = 0; i < P; i++) for (int w = 0; w < pr.nwall; w++) vsta = fmax(vsta, pos(vals[e0 + (i * K + k) * pr.nwall + w])); }
-            e0 += pr.wall_len;
-            if (pr.circ_len) { for (int i = 0; i < P; i++) for (int w = 0; w < pr.ncirc; w++) vsta = fmax(vsta, pos(vals[e0 + (i * K + k) * pr.ncirc + w])); }
-            e0 += pr.circ_len;
-            if (pr.wall3_len) { for (int i = 0; i < P; i++) for (int w = 0; w < pr.nwall3; w++) vsta = fmax(vsta, pos(vals[e0 + (i * K + k) * pr.nwall3 + w])); }
-            e0 += pr.wall3_len;
-            if (pr.cyl_len)  { for (int i = 0; i < P; i++) for (int w = 0; w < pr.ncyl; w++) vsta = fmax(vsta, pos(vals[e0 + (i * K + k) * pr.ncyl + w])); }
-        }
-        o[2 * K + j] = vsta; o[2 * K + N + j] = vopt;
     }
 }
+
+// The handle's shared scenario image: the Params values and the extended-constraint table at the SC_* offsets of algames_device.hpp
+void scen_image(const Handle* hd, double* blk) {
+    const Params& p = hd->pr;
+    for (int e = 0; e < hd->scen_stride; e++) blk[e] = 0.0;
+    for (int e = 0; e < MAXP * MAXP; e++) blk[SC_CAR + e] = p.ca_pair_r[e];
+    for (int e = 0; e < MAXP; e++) { blk[SC_CCR + e] = p.cc_radius[e]; blk[SC_CCM + e] = p.cc_mu[e]; }
+    for (int e = 0; e < MAXM; e++) { blk[SC_UMAX + e] = p.umax[e]; blk[SC_UMIN + e] = p.umin[e]; }
+    for (size_t e = 0; e < hd->extc.size(); e++) blk[SC_EXT + e] = hd->extc[e];
+}
+
+// After every adder of an EXT handle: the shared image is uploaded again and any per-game scenario data is dropped (the kernels read
+// the shared image from then on).  Nothing to upload for a base handle: its kernels read Params -- one that ran the block-reading twins
+// of the base kernels (ext = 2) runs the base kernels again.
+int scen_commit(Handle* hd) {
+    Params& p = hd->pr;
+    if (!hd->keep_sched) sched_drop_all(hd);       // an adder drops every schedule, as it drops per-game data
+    hd->scen_kinds = 0;
+    p.scen = hd->d_scen; p.scen_stride = 0;
+    if (p.ext == 2) p.ext = 0;
+    if (p.ext != 1) return ALG_OK;
+    int rc = use_device(hd); if (rc) return rc;
+    std::vector<double> img((size_t)hd->scen_stride);
+    scen_image(hd, img.data());
+    return h2d(hd, hd->d_scen, img.data(), sizeof(double) * img.size());
+}
+
+// add_collision_avoidance!(game_con, i, j, radius) (constraints_methods.jl:5-19): ONE ordered pair with its own radius
+int add_pair(Handle* hd, const char* who, int i, int j, double radius, int dim) {
+    Params& p = hd->pr;
+    if (i < 0 || j < 0 || i >= p.p || j >= p.p || i == j) return fail(ALG_ERR_ARG, std::string(who) + ": players i != j in 0..p-1");
+    if (!(radius > 0.0)) return fail(ALG_ERR_ARG, std::string(who) + ": radius must be positive");
+    if (p.has_colavoid && p.ca_dim != dim) return fail(ALG_ERR_ARG, std::string(who) + ": planar and spherical collision avoidance cannot be mixed on one handle");
+    if (!p.has_colavoid) for (int a = 0; a < MAXP; a++) p.ca_mask[a] = 0u;
+    if ((p.ca_mask[i] >> j) & 1u) return fail(ALG_ERR_ARG, std::string(who) + ": this ordered pair already carries a collision-avoidance constraint (one per pair)");
+    p.ca_mask[i] |= 1u << j; p.ca_pair_r[i * MAXP + j] = radius;
+    p.has_colavoid = 1; p.ca_dim = dim;
+    return ALG_OK;
+}
+
+// ---- extended ingredient set (examples/intro_example.jl): switches the handle to the EXT kernel instantiation ----------
+int ext_commit(Handle* hd) {
+    // the constraint vectors grew: re-create the constraint arena (mu = rho_0, lam = 0 like a freshly built ALConVal) and push the constants
+    int rc = use_device(hd); if (rc) return rc;
+    if ((rc = sync(hd))) return rc;
+    Params& p = hd->pr;
+    if (!cfg_supported(p, 1)) return fail(ALG_ERR_ARG, "extended constraints: (model, p, d) has no compiled EXT kernel instantiation (DoubleIntegrator d=2 / Unicycle / Bicycle p<=10, DoubleIntegrator d=3 / Quadrotor p<=4)");
+    p.ext = 1;
+    recount_con(p);
+    dfree(hd, p.con); p.con = nullptr;
+    if ((rc = alloc_con(hd))) return rc;
+    if ((rc = scen_commit(hd))) return rc;
+    hipLaunchKernelGGL(k_reset_con, dim3(p.B), dim3(WAVE), 0, hd->stream, hd->pr);
+    if ((rc = launch_check("k_reset_con"))) return rc;
+    return sync(hd);
+}
+
+int need_3d(Handle* hd, const char* who) {
+    if (!(hd->pr.model == ALG_MODEL_QUADROTOR || (hd->pr.model == ALG_MODEL_DOUBLE_INTEGRATOR && hd->pr.d == 3))) {
+        return fail(ALG_ERR_ARG, std::string(who) + ": needs a model with three position dimensions (DoubleIntegrator d = 3, Quadrotor)");
+    }
+    return ALG_OK;
+}
+
+// ---- the four extended-constraint tables of Handle::extc ---------------------------------------------------------------
+// extc = [state bounds (2 p n) | 2-D walls | circles | 3-D walls | cylinders].  A table holds up to `cap` entries of `es` doubles, field-major
+// (field f of entry e at f * cap + e: the planar kinds) or entry-major (es * e + f: the 3-D kinds); Params carries its entry count and,
+// per player, the mask of the entries that constrain that player.
+struct ExtTable {
+    int off, es, cap;
+    bool field_major;
+    int Params::*count;
+    unsigned (Params::*mask)[MAXP];
+    int at(int e, int f) const { return off + (field_major ? f * cap + e : es * e + f); }
+};
+enum { TAB_WALL, TAB_CIRCLE, TAB_WALL3D, TAB_CYLINDER };
+ExtTable ext_table(const Params& p, int which) {
+    const ExtTable t[4] = {{0, 6, ALG_MAX_WALLS, true, &Params::nwall, &Params::wall_mask}, {0, 3, ALG_MAX_CIRCLES, true, &Params::ncirc, &Params::circ_mask},
+                           {0, 12, ALG_MAX_WALLS, false, &Params::nwall3, &Params::wall3_mask}, {0, 6, ALG_MAX_CIRCLES, false, &Params::ncyl, &Params::cyl_mask}};
+    ExtTable r = t[which];
+    r.off = 2 * p.p * p.n;
+    for (int k = 0; k < which; k++) r.off += t[k].es * t[k].cap;
+    return r;
+}
+// The adders hand their entries over as entry-major rows: from one array per field (walls, circles), from the points of 3-D walls, from
+// the (p, axis, l, r) of cylinders
+std::vector<double> rows_of_fields(std::initializer_list<const double*> src, int cnt) {
+    const int F = (int)src.size();
+    std::vector<double> rows((size_t)F * cnt);
+    int f = 0;
+    for (const double* a : src) { for (int w = 0; w < cnt; w++) rows[F * w + f] = a[w]; f++; }
+    return rows;
+}
+std::vector<double> rows_of_walls3d(int nw, const double* p1, const double* p2, const double* p3, const double* v) {
+    std::vector<double> rows(12 * (size_t)nw);
+    for (int w = 0; w < nw; w++) for (int a = 0; a < 3; a++) { rows[12 * w + a] = p1[3 * w + a]; rows[12 * w + 3 + a] = p2[3 * w + a]; rows[12 * w + 6 + a] = p3[3 * w + a]; rows[12 * w + 9 + a] = v[3 * w + a]; }
+    return rows;
+}
+std::vector<double> rows_of_cylinders(int nc, const double* pp, const int32_t* axis, const double* l, const double* r) {
+    std::vector<double> rows(6 * (size_t)nc);
+    for (int c = 0; c < nc; c++) { for (int a = 0; a < 3; a++) rows[6 * c + a] = pp[3 * c + a]; rows[6 * c + 3] = (double)axis[c]; rows[6 * c + 4] = l[c]; rows[6 * c + 5] = r[c]; }
+    return rows;
+}
+// The all-player form of an adder: the rows overwrite the table from its first entry, one set for every player
+int table_set(Handle* hd, int which, const std::vector<double>& rows, int cnt) {
+    Params& p = hd->pr;
+    const ExtTable t = ext_table(p, which);
+    for (int e = 0; e < cnt; e++) for (int f = 0; f < t.es; f++) hd->extc[t.at(e, f)] = rows[t.es * e + f];
+    p.*t.count = cnt;
+    for (int i = 0; i < MAXP; i++) (p.*t.mask)[i] = 0xffffffffu;
+    return ext_commit(hd);
+}
+// The per-player form (add_wall_constraint!(game_con, i, walls), add_circle_constraint!(game_con, i, ...): constraints_methods.jl:121-139,
+// 161-187, 208-299): the entries join the handle's table (identical entries are shared) and set the player's mask bit.
+// Nothing is touched unless every new entry fits: the table is extended on a copy first (of all of extc, a few hundred doubles: simpler
+// than cutting the one table out, and the rest comes back as it was).  After an all-player set (every mask = all ones) the masks are
+// first made explicit, so that an entry added for one player does not silently constrain the others.
+int table_add(Handle* hd, const char* who, int which, const std::vector<double>& rows, int cnt, int player) {
+    Params& p = hd->pr;
+    const ExtTable t = ext_table(p, which);
+    const int ntab = p.*t.count;
+    unsigned* mask = p.*t.mask;
+    std::vector<double> tmp(hd->extc); unsigned m2[MAXP];
+    for (int i = 0; i < MAXP; i++) m2[i] = ntab == 0 ? 0u : (mask[i] == 0xffffffffu ? (ntab >= 32 ? 0xffffffffu : (1u << ntab) - 1u) : mask[i]);
+    int n2 = ntab;
+    for (int w = 0; w < cnt; w++) {
+        int at = -1;
+        for (int e = 0; e < n2 && at < 0; e++) { bool same = true; for (int f = 0; f < t.es; f++) same &= (tmp[t.at(e, f)] == rows[t.es * w + f]); if (same) at = e; }
+        if (at < 0) {
+            if (n2 >= t.cap) return fail(ALG_ERR_ARG, std::string(who) + ": more distinct entries than the table holds (ALG_MAX_WALLS / ALG_MAX_CIRCLES)");
+            at = n2++;
+            for (int f = 0; f < t.es; f++) tmp[t.at(at, f)] = rows[t.es * w + f];
+        }
+        m2[player] |= 1u << at;
+    }
+    hd->extc.swap(tmp);
+    for (int i = 0; i < MAXP; i++) mask[i] = m2[i];
+    p.*t.count = n2;
+    return ext_commit(hd);
+}
+// ---- per-game scenario data (alg_set_scenario_data) ---------------------------------------------------------------------
+// Block offsets of the per-game values of one kind, in the order of the caller's B x len arrays; empty = the kind was not added.
+std::vector<int> scen_map(const Handle* hd, int kind) {
+    const Params& p = hd->pr;
+    std::vector<int> m;
+    // a table's entries in insertion order, the fields of an entry together (field `skip` left out)
+    auto table = [&](int which, int skip) {
+        const ExtTable t = ext_table(p, which);
+        if (p.ext == 1) for (int e = 0; e < p.*t.count; e++) for (int f = 0; f < t.es; f++) if (f != skip) m.push_back(SC_EXT + t.at(e, f));
+    };
+    switch (kind) {
+    case ALG_SCEN_COLLISION_RADIUS:
+        if (p.has_colavoid) for (int i = 0; i < p.p; i++) for (int j = 0; j < p.p; j++) m.push_back(SC_CAR + i * MAXP + j);
+        break;
+    case ALG_SCEN_COLLISION_COST:
+        if (p.has_colcost) { for (int i = 0; i < p.p; i++) m.push_back(SC_CCR + i); for (int i = 0; i < p.p; i++) m.push_back(SC_CCM + i); }
+        break;
+    case ALG_SCEN_CONTROL_BOUND:
+        if (p.has_ctl) { for (int c = 0; c < p.m; c++) m.push_back(SC_UMAX + c); for (int c = 0; c < p.m; c++) m.push_back(SC_UMIN + c); }
+        break;
+    case ALG_SCEN_STATE_BOUND:
+        if (p.ext == 1 && p.has_sb) for (int e = 0; e < 2 * p.p * p.n; e++) m.push_back(SC_EXT + e);
+        break;
+    case ALG_SCEN_WALL: table(TAB_WALL, -1); break;
+    case ALG_SCEN_CIRCLE: table(TAB_CIRCLE, -1); break;
+    case ALG_SCEN_WALL3D: table(TAB_WALL3D, -1); break;
+    case ALG_SCEN_CYLINDER: table(TAB_CYLINDER, 3); break;       // p (3) l r of each entry; the axis (field 3) stays handle-wide
+    }
+    return m;
+}
+bool scen_kind_ok(int kind) { return kind >= ALG_SCEN_COLLISION_RADIUS && kind <= ALG_SCEN_CYLINDER; }
+// entry e of the collision radii (p x p, row i = first player) is ignored: the diagonal and the pairs that were never added
+bool radius_ignored(const Params& p, size_t e) {
+    const int i = (int)e / p.p, j = (int)e % p.p;
+    return i == j || !((p.ca_mask[i] >> j) & 1u);
+}
+// slot of Handle::sched that holds the schedule of a kind (the ALG_SCEN_* kinds keep their number, the LQR targets take the last)
+int sched_slot(int kind) { return kind == ALG_SCHED_LQR_TARGET ? ALG_SCHED_MAX_KINDS - 1 : kind; }
+
+// The rules every game's values of one kind must meet (alg_set_scenario_data; every row of alg_mpc_set_schedule): `data` = B x L values in the
+// order of `map`, `img` = the handle's shared image.  row >= 0 names the schedule row in the message.
+int scen_validate(const Handle* hd, const char* who, int kind, const std::vector<int>& map, const std::vector<double>& img, const double* data, int row) {
+    const Params& p = hd->pr;
+    const size_t L = map.size();
+    const bool bounds = kind == ALG_SCEN_CONTROL_BOUND || kind == ALG_SCEN_STATE_BOUND;
+    for (int g = 0; g < p.B; g++) {
+        const double* v = data + (size_t)g * L;
+        auto bad = [&](const std::string& what, size_t e) {
+            return fail(ALG_ERR_ARG, std::string(who) + ": " + (row >= 0 ? "row " + std::to_string(row) + ", " : std::string()) + "game " + std::to_string(g) + ", entry " + std::to_string(e) + ": " + what);
+        };
+        for (size_t e = 0; e < L; e++) {
+            const double s0 = img[map[e]];
+            if (kind == ALG_SCEN_COLLISION_RADIUS) {
+                if (radius_ignored(p, e)) continue;
+                if (!(v[e] > 0.0) || !std::isfinite(v[e])) return bad("the radius of a pair must be positive and finite", e);
+                continue;
+            }
+            if (bounds) {
+                if (std::isfinite(s0) != std::isfinite(v[e]) || (!std::isfinite(s0) && !(s0 == v[e])))
+                    return bad("the +-inf pattern of the bounds differs from the handle's", e);
+                continue;
+            }
+            if (std::isfinite(s0) && !std::isfinite(v[e])) return bad("non-finite value where the handle's is finite", e);
+            if ((kind == ALG_SCEN_CIRCLE && e % 3 == 2) || (kind == ALG_SCEN_CYLINDER && e % 5 == 4))
+                if (!(v[e] > 0.0)) return bad("radius must be positive", e);
+        }
+        if (bounds) for (size_t e = 0; e < L / 2; e++) if (!(v[e] >= v[L / 2 + e])) return bad("Upper bounds must be greater than or equal to lower bounds", e);
+    }
+    return ALG_OK;
+}
+
+// alg_set_scenario_data without the bookkeeping of schedules (alg_mpc_set_schedule makes a kind per-game through it, with row 0)
+int set_scenario_data(alg_handle* h, const char* who, int32_t kind, const double* data, bool validate) {
+    Params& p = H->pr;
+    const std::vector<int> map = scen_map(H, kind);
+    if (map.empty()) return fail(ALG_ERR_STATE, std::string(who) + ": this kind of constraint / cost was not added to the handle");
+    const size_t L = map.size(), SS = (size_t)H->scen_stride;
+    std::vector<double> img(SS);
+    scen_image(H, img.data());
+    int rc = use_device(H); if (rc) return rc;
+    if (!data) {                  // back to the shared values
+        if (!((H->scen_kinds >> kind) & 1u)) return ALG_OK;
+        H->scen_kinds &= ~(1u << kind);
+        if (!H->scen_kinds) { p.scen = H->d_scen; p.scen_stride = 0; if (p.ext == 2) p.ext = 0; return ALG_OK; }
+        for (int g = 0; g < p.B; g++) for (size_t e = 0; e < L; e++) H->scen_games[g * SS + map[e]] = img[map[e]];
+        return h2d(H, H->d_scen_games, H->scen_games.data(), sizeof(double) * SS * p.B);
+    }
+    // validation of every game before anything changes
+    if (validate && (rc = scen_validate(H, who, kind, map, img, data, -1))) return rc;
+    // the first per-game call of a base handle switches it to the EXT instantiation (multipliers re-created like every extended adder) --
+    // unless the handle was told to stay on the base kernels (alg_set_scenario_kernels): then nothing but the blocks changes, and the
+    // handle runs the twins of the base kernels that read them (ext = 2) while any kind is per game
+    const bool stay_base = p.ext != 1 && H->scen_kernels == ALG_SCEN_KERNELS_BASE;
+    if (!p.ext && !stay_base) {
+        H->keep_sched = true; rc = ext_commit(H); H->keep_sched = false;
+        if (rc) return rc;
+    }
+    if (!H->scen_kinds) {
+        if (!H->d_scen_games && (rc = dalloc(H, &H->d_scen_games, SS * p.B, "scenario blocks (per game)"))) return rc;
+        H->scen_games.resize(SS * p.B);
+        for (int g = 0; g < p.B; g++) std::copy(img.begin(), img.end(), H->scen_games.begin() + g * SS);
+    }
+    for (int g = 0; g < p.B; g++) {
+        for (size_t e = 0; e < L; e++) {
+            if (kind == ALG_SCEN_COLLISION_RADIUS && radius_ignored(p, e)) continue;
+            H->scen_games[g * SS + map[e]] = data[(size_t)g * L + e];
+        }
+    }
+    if ((rc = h2d(H, H->d_scen_games, H->scen_games.data(), sizeof(double) * SS * p.B))) return rc;
+    H->scen_kinds |= 1u << kind;
+    p.scen = H->d_scen_games; p.scen_stride = (int)SS;
+    if (stay_base) p.ext = 2;
+    return ALG_OK;
+}
+
+// The loop of alg_mpc_solve and alg_mpc_solve_log; `who` names the entry point in the error messages
+int mpc_solve_impl(const char* who, alg_handle* h, int32_t steps, int64_t game_id0, double* states, double* controls, alg_game_stats* stats) {
+    if (!h || steps < 1) return fail(ALG_ERR_ARG, std::string(who) + ": bad argument");
+    int rc = use_device(H); if (rc) return rc;
+    if (!H->x0_set || !H->lqr_set) return fail(ALG_ERR_STATE, std::string(who) + ": x0 / LQR data not set");
+    const Params& p = H->pr;
+    // one scratch allocation for all requested outputs: [states | controls | stats], every part 8-byte aligned; under a plant (alg_mpc_set_plant)
+    // states and controls hold one row per plant knot, steps x hold of them
+    const size_t knots = (size_t)steps * (size_t)H->plant.hold;
+    const bool planted = !mpc_plant_is_default(H->plant.hold, H->plant.substeps, H->plant.integrator);
+    const size_t b_st = states ? sizeof(double) * (knots + 1) * p.B * p.n : 0, b_uc = controls ? sizeof(double) * knots * p.B * p.m : 0,
+                 b_gs = stats ? sizeof(alg_game_stats) * (size_t)steps * p.B : 0;
+    static_assert(sizeof(alg_game_stats) % 8 == 0, "the stats log follows doubles in the scratch");
+    if (b_st + b_uc + b_gs && (rc = ensure_scratch(H, b_st + b_uc + b_gs))) return rc;
+    char* const d0 = (char*)H->d_scratch;
+    double* const d_states = states ? (double*)d0 : nullptr;
+    double* const d_controls = controls ? (double*)(d0 + b_st) : nullptr;
+    alg_game_stats* const d_stats = stats ? (alg_game_stats*)(d0 + b_st + b_uc) : nullptr;
+    bool scheduled = false;
+    for (int k = 0; k < ALG_SCHED_MAX_KINDS; k++) scheduled |= H->sched[k].rows > 0;
+    // the sibling kernels are the loop with per-step phases: a schedule, a disturbance, a log or a plant takes them
+    if (!scheduled && !H->dist.rows && !controls && !stats && !planted) rc = launch_mpc_loop(H, (int)steps, (uint64_t)game_id0, d_states);
+    else rc = launch_mpc_loop_sched(H, (int)steps, (uint64_t)game_id0, d_states, d_controls, d_stats);
+    if (rc) return rc;
+    // the loop leaves the row its last step used in the games' blocks: the host mirror of the scenario blocks follows (what the step-wise
+    // alg_set_scenario_data calls would have left; the LQR blocks have no host mirror)
+    for (int k = 0; scheduled && k < ALG_SCHED_MAX_KINDS - 1; k++) {
+        const Handle::Sched& sc = H->sched[k];
+        if (!sc.rows) continue;
+        const size_t row = (size_t)std::min((int)steps - 1, sc.rows - 1), SS = (size_t)H->scen_stride;
+        for (int g = 0; g < p.B; g++)
+            for (int e = 0; e < sc.len; e++)
+                if (sc.map[e] >= 0) H->scen_games[g * SS + sc.map[e]] = sc.data[(row * p.B + g) * sc.len + e];
+    }
+    // one copy back per output (each waits for the stream: the call is synchronous as soon as one output is asked for)
+    if (states && (rc = d2h(H, states, d_states, b_st))) return rc;
+    if (controls && (rc = d2h(H, controls, d_controls, b_uc))) return rc;
+    if (stats && (rc = d2h(H, stats, d_stats, b_gs))) return rc;
+    return ALG_OK;
+}
+
+// The plant disturbance (ALG_SCHED_DISTURBANCE): rows x B x n, needs nothing of the handle but its sizes
+int set_disturbance(Handle* hd, int32_t rows, const double* data) {
+    int rc = use_device(hd); if (rc) return rc;
+    if (!data) { sched_drop(hd, hd->dist); return ALG_OK; }
+    if (rows < 1) return fail(ALG_ERR_ARG, "alg_mpc_set_schedule: rows must be >= 1");
+    const Params& p = hd->pr;
+    const size_t per_row = (size_t)p.B * p.n, cnt = (size_t)rows * per_row;
+    for (size_t e = 0; e < cnt; e++)
+        if (!std::isfinite(data[e])) return fail(ALG_ERR_ARG, "alg_mpc_set_schedule: row " + std::to_string(e / per_row) + ": disturbances must be finite");
+    Handle::Sched sc;
+    sc.rows = rows; sc.len = p.n;
+    if ((rc = dalloc(hd, &sc.d_data, cnt, "disturbance rows"))) return rc;
+    if ((rc = h2d(hd, sc.d_data, data, sizeof(double) * cnt))) { dfree(hd, sc.d_data); return rc; }
+    sched_drop(hd, hd->dist);
+    hd->dist = std::move(sc);
+    return ALG_OK;
+}
+
+} // namespace
 
 #define NEED_HANDLE(name) do { if (!h) return fail(ALG_ERR_ARG, name ": null handle"); } while (0)
 
@@ -563,7 +873,7 @@ int alg_set_waves_per_game(alg_handle* h, int32_t nw) {
     if (nw != 0 && nw != 1 && nw != 2 && nw != 4) return fail(ALG_ERR_ARG, "alg_set_waves_per_game: 0 (automatic), 1, 2 or 4");
     const int prev = H->waves_per_game;
     H->waves_per_game = nw;
-    if (team_width(H) < 0) { H->waves_per_game = prev; return fail(ALG_ERR_ARG, "alg_set_waves_per_game: no team kernel of that width is compiled for this configuration"); }
+    if (team_width(H) < 0) { H->waves_per_game = prev; return fail(ALG_ERR_ARG, NO_TEAM_WIDTH); }
     return ALG_OK;
 }
 int alg_set_refinement(alg_handle* h, int32_t max_steps, double tol, double mu_tight) {
@@ -589,12 +899,7 @@ int alg_set_handoff(alg_handle* h, int32_t iters) {
     NEED_HANDLE("alg_set_handoff");
     if (iters < 0) return fail(ALG_ERR_ARG, "alg_set_handoff: iterations >= 0 (0 = off)");
     if (iters > 0) {
-        bool have = false;
-#define X(M, P, D, E, W) if (H->pr.model == (M) && H->pr.p == (P) && H->pr.d == (D) && H->pr.ext == (E)) have = true;
-        ALG_CFGS_HANDOFF(X)
-        ALG_CFGS_HANDOFF_SCEN(X)
-#undef X
-        if (!have) return fail(ALG_ERR_ARG, "alg_set_handoff: no hand-off kernel pair is compiled for this configuration (3-player DoubleIntegrator d = 2, 3- / 4-player Unicycle, base constraint set on the base kernels)");
+        if (!dispatch_handoff(H->pr, [](auto, auto) {})) return fail(ALG_ERR_ARG, "alg_set_handoff: no hand-off kernel pair is compiled for this configuration (3-player DoubleIntegrator d = 2, 3- / 4-player Unicycle, base constraint set on the base kernels)");
         if (!H->d_ho) {
             int rc = use_device(H); if (rc) return rc;
             if ((rc = dalloc(H, &H->d_ho, (size_t)H->pr.B + 1, "hand-off queue"))) return rc;
@@ -644,46 +949,10 @@ int alg_set_lqr(alg_handle* h, const double* Qd, const double* Rd, const double*
     if ((rc = sync(H))) return rc;
     p.lqr_per_game = per_game ? 1 : 0; p.lqr_stride = per_game ? blk : 0;
     H->lqr_set = true;
-    sched_drop(H, ALG_SCHED_MAX_KINDS - 1);        // the target schedule goes with the data it was set against
+    sched_drop(H, sched_slot(ALG_SCHED_LQR_TARGET));   // the target schedule goes with the data it was set against
     return ALG_OK;
 }
 
-// the vector form of the adders: every ordered pair (i, j), radius r_i + r_j (constraints_methods.jl:21-33)
-void set_all_pairs(Params& p, const double* radius) {
-    for (int i = 0; i < MAXP; i++) {
-        p.ca_mask[i] = 0u;
-        for (int j = 0; j < MAXP; j++) {
-            p.ca_pair_r[i * MAXP + j] = 0.0;
-            if (i < p.p && j < p.p && i != j) { p.ca_pair_r[i * MAXP + j] = radius[i] + radius[j]; p.ca_mask[i] |= 1u << j; }
-        }
-    }
-}
-static int need_3d(Handle* hd, const char* who);
-static int ext_commit(Handle* hd);
-// The handle's shared scenario image: the Params values and the extended-constraint table at the SC_* offsets of algames_device.hpp
-static void scen_image(const Handle* hd, double* blk) {
-    const Params& p = hd->pr;
-    for (int e = 0; e < hd->scen_stride; e++) blk[e] = 0.0;
-    for (int e = 0; e < MAXP * MAXP; e++) blk[SC_CAR + e] = p.ca_pair_r[e];
-    for (int e = 0; e < MAXP; e++) { blk[SC_CCR + e] = p.cc_radius[e]; blk[SC_CCM + e] = p.cc_mu[e]; }
-    for (int e = 0; e < MAXM; e++) { blk[SC_UMAX + e] = p.umax[e]; blk[SC_UMIN + e] = p.umin[e]; }
-    for (size_t e = 0; e < hd->extc.size(); e++) blk[SC_EXT + e] = hd->extc[e];
-}
-// After every adder of an EXT handle: the shared image is uploaded again and any per-game scenario data is dropped (the kernels read
-// the shared image from then on).  Nothing to upload for a base handle: its kernels read Params -- one that ran the block-reading twins
-// of the base kernels (ext = 2) runs the base kernels again.
-static int scen_commit(Handle* hd) {
-    Params& p = hd->pr;
-    if (!hd->keep_sched) sched_drop_all(hd);       // an adder drops every schedule, as it drops per-game data
-    hd->scen_kinds = 0;
-    p.scen = hd->d_scen; p.scen_stride = 0;
-    if (p.ext == 2) p.ext = 0;
-    if (p.ext != 1) return ALG_OK;
-    int rc = use_device(hd); if (rc) return rc;
-    std::vector<double> img((size_t)hd->scen_stride);
-    scen_image(hd, img.data());
-    return h2d(hd, hd->d_scen, img.data(), sizeof(double) * img.size());
-}
 int alg_add_collision_cost(alg_handle* h, const double* radius, const double* mu) {
     NEED_HANDLE("alg_add_collision_cost");
     Params& p = H->pr;
@@ -697,18 +966,6 @@ int alg_add_collision_avoidance(alg_handle* h, const double* radius) {
     if (!radius) { p.has_colavoid = 0; return scen_commit(H); }
     set_all_pairs(p, radius);
     p.has_colavoid = 1; p.ca_dim = 2; return scen_commit(H);
-}
-// add_collision_avoidance!(game_con, i, j, radius) (constraints_methods.jl:5-19): ONE ordered pair with its own radius
-int add_pair(Handle* hd, const char* who, int i, int j, double radius, int dim) {
-    Params& p = hd->pr;
-    if (i < 0 || j < 0 || i >= p.p || j >= p.p || i == j) return fail(ALG_ERR_ARG, std::string(who) + ": players i != j in 0..p-1");
-    if (!(radius > 0.0)) return fail(ALG_ERR_ARG, std::string(who) + ": radius must be positive");
-    if (p.has_colavoid && p.ca_dim != dim) return fail(ALG_ERR_ARG, std::string(who) + ": planar and spherical collision avoidance cannot be mixed on one handle");
-    if (!p.has_colavoid) for (int a = 0; a < MAXP; a++) p.ca_mask[a] = 0u;
-    if ((p.ca_mask[i] >> j) & 1u) return fail(ALG_ERR_ARG, std::string(who) + ": this ordered pair already carries a collision-avoidance constraint (one per pair)");
-    p.ca_mask[i] |= 1u << j; p.ca_pair_r[i * MAXP + j] = radius;
-    p.has_colavoid = 1; p.ca_dim = dim;
-    return ALG_OK;
 }
 int alg_add_collision_avoidance_pair(alg_handle* h, int32_t i, int32_t j, double radius) {
     NEED_HANDLE("alg_add_collision_avoidance_pair");
@@ -742,30 +999,14 @@ int alg_add_control_bound(alg_handle* h, const double* umax, const double* umin)
     p.has_ctl = 1; return scen_commit(H);
 }
 
-// ---- extended ingredient set (examples/intro_example.jl): switches the handle to the EXT kernel instantiation ----------
-static int ext_commit(Handle* hd) {
-    // the constraint vectors grew: re-create the constraint arena (mu = rho_0, lam = 0 like a freshly built ALConVal) and push the constants
-    int rc = use_device(hd); if (rc) return rc;
-    if ((rc = sync(hd))) return rc;
-    Params& p = hd->pr;
-    if (!cfg_supported(p, 1)) return fail(ALG_ERR_ARG, "extended constraints: (model, p, d) has no compiled EXT kernel instantiation (DoubleIntegrator d=2 / Unicycle / Bicycle p<=10, DoubleIntegrator d=3 / Quadrotor p<=4)");
-    p.ext = 1;
-    recount_con(p);
-    dfree(hd, p.con); p.con = nullptr;
-    if ((rc = alloc_con(hd))) return rc;
-    if ((rc = scen_commit(hd))) return rc;
-    hipLaunchKernelGGL(k_reset_con, dim3(p.B), dim3(WAVE), 0, hd->stream, hd->pr);
-    if ((rc = launch_check("k_reset_con"))) return rc;
-    return sync(hd);
-}
 int alg_set_quadrotor(alg_handle* h, double mass) {
-    if (!h) return fail(ALG_ERR_ARG, "alg_set_quadrotor: null handle");
+    NEED_HANDLE("alg_set_quadrotor");
     if (H->pr.model != ALG_MODEL_QUADROTOR) return fail(ALG_ERR_ARG, "alg_set_quadrotor: not a quadrotor model");
     if (!(mass > 0)) return fail(ALG_ERR_ARG, "alg_set_quadrotor: mass must be positive");
     H->pr.qmass = mass; return ALG_OK;
 }
 int alg_set_bicycle(alg_handle* h, double lf, double lr) {
-    if (!h) return fail(ALG_ERR_ARG, "alg_set_bicycle: null handle");
+    NEED_HANDLE("alg_set_bicycle");
     if (H->pr.model != ALG_MODEL_BICYCLE) return fail(ALG_ERR_ARG, "alg_set_bicycle: not a bicycle model");
     if (!(lr > 0) || !(lf >= 0)) return fail(ALG_ERR_ARG, "alg_set_bicycle: bad lengths");
     H->pr.lf = lf; H->pr.lr = lr; return ALG_OK;
@@ -781,102 +1022,32 @@ int alg_add_state_bound(alg_handle* h, int32_t player, const double* xmax, const
     p.has_sb = 1;
     return ext_commit(H);
 }
+// Walls, circles, 3-D walls, cylinders: the all-player form sets the kind's table (table_set), the per-player form adds to it (table_add)
 int alg_add_wall_constraint(alg_handle* h, int32_t nw, const double* x1, const double* y1, const double* x2, const double* y2, const double* xv, const double* yv) {
-    if (!h) return fail(ALG_ERR_ARG, "alg_add_wall_constraint: null handle");
+    NEED_HANDLE("alg_add_wall_constraint");
     if (nw < 0 || nw > ALG_MAX_WALLS || (nw > 0 && (!x1 || !y1 || !x2 || !y2 || !xv || !yv))) return fail(ALG_ERR_ARG, "alg_add_wall_constraint: bad argument (at most ALG_MAX_WALLS walls)");
-    Params& p = H->pr;
-    double* W = H->extc.data() + 2 * p.p * p.n;
-    const double* src[6] = {x1, y1, x2, y2, xv, yv};
-    for (int f = 0; f < 6; f++) for (int w = 0; w < nw; w++) W[f * ALG_MAX_WALLS + w] = src[f][w];
-    p.nwall = nw;
-    for (int i = 0; i < MAXP; i++) p.wall_mask[i] = 0xffffffffu;      // one set, every player
-    return ext_commit(H);
-}
-// add_wall_constraint!(game_con, i, walls) (constraints_methods.jl:161-187): the walls join the table (an entry that is already
-// there is shared) and constrain player `player` only
-// Per-player wall / circle sets: the entries join the handle's table (identical entries are shared) and set the player's mask bit.
-// Nothing is touched unless every new entry fits (the table is extended on a copy first).  After an all-player set
-// (alg_add_wall_constraint / alg_add_circle_constraint: every mask = all ones) the masks are first made explicit, so that an entry
-// added for one player does not silently constrain the others.
-static int add_table_entries(int F, int MAXE, Handle* hd, const char* who, double* T, const double* const* src, int cnt, int player, int& ntab, unsigned* mask) {
-    std::vector<double> tmp(T, T + F * MAXE); unsigned m2[MAXP];
-    for (int i = 0; i < MAXP; i++) m2[i] = ntab == 0 ? 0u : (mask[i] == 0xffffffffu ? (ntab >= 32 ? 0xffffffffu : (1u << ntab) - 1u) : mask[i]);
-    int n2 = ntab;
-    for (int w = 0; w < cnt; w++) {
-        int at = -1;
-        for (int e = 0; e < n2 && at < 0; e++) { bool same = true; for (int f = 0; f < F; f++) same &= (tmp[f * MAXE + e] == src[f][w]); if (same) at = e; }
-        if (at < 0) {
-            if (n2 >= MAXE) return fail(ALG_ERR_ARG, std::string(who) + ": more distinct entries than the table holds (ALG_MAX_WALLS / ALG_MAX_CIRCLES)");
-            at = n2++;
-            for (int f = 0; f < F; f++) tmp[f * MAXE + at] = src[f][w];
-        }
-        m2[player] |= 1u << at;
-    }
-    for (int e = 0; e < F * MAXE; e++) T[e] = tmp[e];
-    for (int i = 0; i < MAXP; i++) mask[i] = m2[i];
-    ntab = n2;
-    return ext_commit(hd);
-}
-// the same for tables that keep an entry's ES doubles together (3-D walls: 12 per wall, cylinders: 6 per cylinder); `rows` = the new
-// entries in that layout
-static int add_table_rows(int ES, int MAXE, Handle* hd, const char* who, double* T, const double* rows, int cnt, int player, int& ntab, unsigned* mask) {
-    std::vector<double> tmp(T, T + ES * MAXE); unsigned m2[MAXP];
-    for (int i = 0; i < MAXP; i++) m2[i] = ntab == 0 ? 0u : (mask[i] == 0xffffffffu ? (ntab >= 32 ? 0xffffffffu : (1u << ntab) - 1u) : mask[i]);
-    int n2 = ntab;
-    for (int w = 0; w < cnt; w++) {
-        int at = -1;
-        for (int e = 0; e < n2 && at < 0; e++) { bool same = true; for (int f = 0; f < ES; f++) same &= (tmp[ES * e + f] == rows[ES * w + f]); if (same) at = e; }
-        if (at < 0) {
-            if (n2 >= MAXE) return fail(ALG_ERR_ARG, std::string(who) + ": more distinct entries than the table holds (ALG_MAX_WALLS / ALG_MAX_CIRCLES)");
-            at = n2++;
-            for (int f = 0; f < ES; f++) tmp[ES * at + f] = rows[ES * w + f];
-        }
-        m2[player] |= 1u << at;
-    }
-    for (int e = 0; e < ES * MAXE; e++) T[e] = tmp[e];
-    for (int i = 0; i < MAXP; i++) mask[i] = m2[i];
-    ntab = n2;
-    return ext_commit(hd);
+    return table_set(H, TAB_WALL, rows_of_fields({x1, y1, x2, y2, xv, yv}, nw), nw);
 }
 int alg_add_wall_constraint_player(alg_handle* h, int32_t player, int32_t nw, const double* x1, const double* y1, const double* x2, const double* y2, const double* xv, const double* yv) {
-    if (!h) return fail(ALG_ERR_ARG, "alg_add_wall_constraint_player: null handle");
-    Params& p = H->pr;
-    if (player < 0 || player >= p.p) return fail(ALG_ERR_ARG, "alg_add_wall_constraint_player: bad player index");
+    NEED_HANDLE("alg_add_wall_constraint_player");
+    if (player < 0 || player >= H->pr.p) return fail(ALG_ERR_ARG, "alg_add_wall_constraint_player: bad player index");
     if (nw < 0 || (nw > 0 && (!x1 || !y1 || !x2 || !y2 || !xv || !yv))) return fail(ALG_ERR_ARG, "alg_add_wall_constraint_player: bad argument");
-    double* W = H->extc.data() + 2 * p.p * p.n;
-    const double* src[6] = {x1, y1, x2, y2, xv, yv};
-    return add_table_entries(6, ALG_MAX_WALLS, H, "alg_add_wall_constraint_player", W, src, nw, player, p.nwall, p.wall_mask);
+    return table_add(H, "alg_add_wall_constraint_player", TAB_WALL, rows_of_fields({x1, y1, x2, y2, xv, yv}, nw), nw, player);
 }
 int alg_add_circle_constraint(alg_handle* h, int32_t nc, const double* xc, const double* yc, const double* rad) {
-    if (!h) return fail(ALG_ERR_ARG, "alg_add_circle_constraint: null handle");
+    NEED_HANDLE("alg_add_circle_constraint");
     if (nc < 0 || nc > ALG_MAX_CIRCLES || (nc > 0 && (!xc || !yc || !rad))) return fail(ALG_ERR_ARG, "alg_add_circle_constraint: bad argument (at most ALG_MAX_CIRCLES circles)");
-    Params& p = H->pr;
-    double* Cc = H->extc.data() + 2 * p.p * p.n + 6 * ALG_MAX_WALLS;
-    const double* src[3] = {xc, yc, rad};
-    for (int f = 0; f < 3; f++) for (int c = 0; c < nc; c++) Cc[f * ALG_MAX_CIRCLES + c] = src[f][c];
-    p.ncirc = nc;
-    for (int i = 0; i < MAXP; i++) p.circ_mask[i] = 0xffffffffu;      // one set, every player
-    return ext_commit(H);
+    return table_set(H, TAB_CIRCLE, rows_of_fields({xc, yc, rad}, nc), nc);
 }
-// add_circle_constraint!(game_con, i, xc, yc, radius) (constraints_methods.jl:121-139): as alg_add_wall_constraint_player
 int alg_add_circle_constraint_player(alg_handle* h, int32_t player, int32_t nc, const double* xc, const double* yc, const double* rad) {
-    if (!h) return fail(ALG_ERR_ARG, "alg_add_circle_constraint_player: null handle");
-    Params& p = H->pr;
-    if (player < 0 || player >= p.p) return fail(ALG_ERR_ARG, "alg_add_circle_constraint_player: bad player index");
+    NEED_HANDLE("alg_add_circle_constraint_player");
+    if (player < 0 || player >= H->pr.p) return fail(ALG_ERR_ARG, "alg_add_circle_constraint_player: bad player index");
     if (nc < 0 || (nc > 0 && (!xc || !yc || !rad))) return fail(ALG_ERR_ARG, "alg_add_circle_constraint_player: bad argument");
-    double* Cc = H->extc.data() + 2 * p.p * p.n + 6 * ALG_MAX_WALLS;
-    const double* src[3] = {xc, yc, rad};
-    return add_table_entries(3, ALG_MAX_CIRCLES, H, "alg_add_circle_constraint_player", Cc, src, nc, player, p.ncirc, p.circ_mask);
+    return table_add(H, "alg_add_circle_constraint_player", TAB_CIRCLE, rows_of_fields({xc, yc, rad}, nc), nc, player);
 }
 // ---- 3-D half (pz[i][1:3] = positions of DoubleIntegrator d = 3) -------------------------------------------------------
-static int need_3d(Handle* hd, const char* who) {
-    if (!(hd->pr.model == ALG_MODEL_QUADROTOR || (hd->pr.model == ALG_MODEL_DOUBLE_INTEGRATOR && hd->pr.d == 3))) {
-        return fail(ALG_ERR_ARG, std::string(who) + ": needs a model with three position dimensions (DoubleIntegrator d = 3, Quadrotor)");
-    }
-    return ALG_OK;
-}
 int alg_add_spherical_collision_avoidance(alg_handle* h, const double* radius) {
-    if (!h) return fail(ALG_ERR_ARG, "alg_add_spherical_collision_avoidance: null handle");
+    NEED_HANDLE("alg_add_spherical_collision_avoidance");
     Params& p = H->pr;
     if (!radius) { p.has_colavoid = 0; p.ca_dim = 2; return scen_commit(H); }
     if (int rc = need_3d(H, "alg_add_spherical_collision_avoidance")) return rc;
@@ -885,88 +1056,33 @@ int alg_add_spherical_collision_avoidance(alg_handle* h, const double* radius) {
     return ext_commit(H);                      // the 3-D pair blocks live in the EXT instantiation
 }
 int alg_add_wall3d_constraint(alg_handle* h, int32_t nw, const double* p1, const double* p2, const double* p3, const double* v) {
-    if (!h) return fail(ALG_ERR_ARG, "alg_add_wall3d_constraint: null handle");
+    NEED_HANDLE("alg_add_wall3d_constraint");
     if (nw < 0 || nw > ALG_MAX_WALLS || (nw > 0 && (!p1 || !p2 || !p3 || !v))) return fail(ALG_ERR_ARG, "alg_add_wall3d_constraint: bad argument (at most ALG_MAX_WALLS walls)");
     if (int rc = need_3d(H, "alg_add_wall3d_constraint")) return rc;
-    Params& p = H->pr;
-    double* W = H->extc.data() + 2 * p.p * p.n + 6 * ALG_MAX_WALLS + 3 * ALG_MAX_CIRCLES;
-    for (int w = 0; w < nw; w++) for (int a = 0; a < 3; a++) { W[12 * w + a] = p1[3 * w + a]; W[12 * w + 3 + a] = p2[3 * w + a]; W[12 * w + 6 + a] = p3[3 * w + a]; W[12 * w + 9 + a] = v[3 * w + a]; }
-    p.nwall3 = nw;
-    for (int i = 0; i < MAXP; i++) p.wall3_mask[i] = 0xffffffffu;     // one set, every player
-    return ext_commit(H);
+    return table_set(H, TAB_WALL3D, rows_of_walls3d(nw, p1, p2, p3, v), nw);
 }
-// add_wall_constraint!(game_con, i, walls::Vector{Wall3D}) (constraints_methods.jl:208-247): table + per-player mask like the 2-D form
 int alg_add_wall3d_constraint_player(alg_handle* h, int32_t player, int32_t nw, const double* p1, const double* p2, const double* p3, const double* v) {
-    if (!h) return fail(ALG_ERR_ARG, "alg_add_wall3d_constraint_player: null handle");
-    Params& p = H->pr;
-    if (player < 0 || player >= p.p) return fail(ALG_ERR_ARG, "alg_add_wall3d_constraint_player: bad player index");
+    NEED_HANDLE("alg_add_wall3d_constraint_player");
+    if (player < 0 || player >= H->pr.p) return fail(ALG_ERR_ARG, "alg_add_wall3d_constraint_player: bad player index");
     if (nw < 0 || (nw > 0 && (!p1 || !p2 || !p3 || !v))) return fail(ALG_ERR_ARG, "alg_add_wall3d_constraint_player: bad argument");
     if (int rc = need_3d(H, "alg_add_wall3d_constraint_player")) return rc;
-    std::vector<double> rows(12 * (size_t)nw);
-    for (int w = 0; w < nw; w++) for (int a = 0; a < 3; a++) { rows[12 * w + a] = p1[3 * w + a]; rows[12 * w + 3 + a] = p2[3 * w + a]; rows[12 * w + 6 + a] = p3[3 * w + a]; rows[12 * w + 9 + a] = v[3 * w + a]; }
-    double* W = H->extc.data() + 2 * p.p * p.n + 6 * ALG_MAX_WALLS + 3 * ALG_MAX_CIRCLES;
-    return add_table_rows(12, ALG_MAX_WALLS, H, "alg_add_wall3d_constraint_player", W, rows.data(), nw, player, p.nwall3, p.wall3_mask);
+    return table_add(H, "alg_add_wall3d_constraint_player", TAB_WALL3D, rows_of_walls3d(nw, p1, p2, p3, v), nw, player);
 }
 int alg_add_cylinder_constraint(alg_handle* h, int32_t nc, const double* pp, const int32_t* axis, const double* l, const double* r) {
-    if (!h) return fail(ALG_ERR_ARG, "alg_add_cylinder_constraint: null handle");
+    NEED_HANDLE("alg_add_cylinder_constraint");
     if (nc < 0 || nc > ALG_MAX_CIRCLES || (nc > 0 && (!pp || !axis || !l || !r))) return fail(ALG_ERR_ARG, "alg_add_cylinder_constraint: bad argument (at most ALG_MAX_CIRCLES cylinders)");
     if (int rc = need_3d(H, "alg_add_cylinder_constraint")) return rc;
     for (int c = 0; c < nc; c++) if (axis[c] < 0 || axis[c] > 2) return fail(ALG_ERR_ARG, "alg_add_cylinder_constraint: axis must be 0 (:x), 1 (:y) or 2 (:z)");
-    Params& p = H->pr;
-    double* Y = H->extc.data() + 2 * p.p * p.n + 6 * ALG_MAX_WALLS + 3 * ALG_MAX_CIRCLES + 12 * ALG_MAX_WALLS;
-    for (int c = 0; c < nc; c++) { for (int a = 0; a < 3; a++) Y[6 * c + a] = pp[3 * c + a]; Y[6 * c + 3] = (double)axis[c]; Y[6 * c + 4] = l[c]; Y[6 * c + 5] = r[c]; }
-    p.ncyl = nc;
-    for (int i = 0; i < MAXP; i++) p.cyl_mask[i] = 0xffffffffu;       // one set, every player
-    return ext_commit(H);
+    return table_set(H, TAB_CYLINDER, rows_of_cylinders(nc, pp, axis, l, r), nc);
 }
-// add_wall_constraint!(game_con, i, walls::Vector{CylinderWall}) (constraints_methods.jl:256-299)
 int alg_add_cylinder_constraint_player(alg_handle* h, int32_t player, int32_t nc, const double* pp, const int32_t* axis, const double* l, const double* r) {
-    if (!h) return fail(ALG_ERR_ARG, "alg_add_cylinder_constraint_player: null handle");
-    Params& p = H->pr;
-    if (player < 0 || player >= p.p) return fail(ALG_ERR_ARG, "alg_add_cylinder_constraint_player: bad player index");
+    NEED_HANDLE("alg_add_cylinder_constraint_player");
+    if (player < 0 || player >= H->pr.p) return fail(ALG_ERR_ARG, "alg_add_cylinder_constraint_player: bad player index");
     if (nc < 0 || (nc > 0 && (!pp || !axis || !l || !r))) return fail(ALG_ERR_ARG, "alg_add_cylinder_constraint_player: bad argument");
     if (int rc = need_3d(H, "alg_add_cylinder_constraint_player")) return rc;
     for (int c = 0; c < nc; c++) if (axis[c] < 0 || axis[c] > 2) return fail(ALG_ERR_ARG, "alg_add_cylinder_constraint_player: axis must be 0 (:x), 1 (:y) or 2 (:z)");
-    std::vector<double> rows(6 * (size_t)nc);
-    for (int c = 0; c < nc; c++) { for (int a = 0; a < 3; a++) rows[6 * c + a] = pp[3 * c + a]; rows[6 * c + 3] = (double)axis[c]; rows[6 * c + 4] = l[c]; rows[6 * c + 5] = r[c]; }
-    double* Y = H->extc.data() + 2 * p.p * p.n + 6 * ALG_MAX_WALLS + 3 * ALG_MAX_CIRCLES + 12 * ALG_MAX_WALLS;
-    return add_table_rows(6, ALG_MAX_CIRCLES, H, "alg_add_cylinder_constraint_player", Y, rows.data(), nc, player, p.ncyl, p.cyl_mask);
+    return table_add(H, "alg_add_cylinder_constraint_player", TAB_CYLINDER, rows_of_cylinders(nc, pp, axis, l, r), nc, player);
 }
-// ---- per-game scenario data (alg_set_scenario_data) ---------------------------------------------------------------------
-// Block offsets of the per-game values of one kind, in the order of the caller's B x len arrays; empty = the kind was not added.
-static std::vector<int> scen_map(const Handle* hd, int kind) {
-    const Params& p = hd->pr;
-    std::vector<int> m;
-    const int ew = SC_EXT + 2 * p.p * p.n, ec = ew + 6 * ALG_MAX_WALLS, e3 = ec + 3 * ALG_MAX_CIRCLES, ey = e3 + 12 * ALG_MAX_WALLS;
-    switch (kind) {
-    case ALG_SCEN_COLLISION_RADIUS:
-        if (p.has_colavoid) for (int i = 0; i < p.p; i++) for (int j = 0; j < p.p; j++) m.push_back(SC_CAR + i * MAXP + j);
-        break;
-    case ALG_SCEN_COLLISION_COST:
-        if (p.has_colcost) { for (int i = 0; i < p.p; i++) m.push_back(SC_CCR + i); for (int i = 0; i < p.p; i++) m.push_back(SC_CCM + i); }
-        break;
-    case ALG_SCEN_CONTROL_BOUND:
-        if (p.has_ctl) { for (int c = 0; c < p.m; c++) m.push_back(SC_UMAX + c); for (int c = 0; c < p.m; c++) m.push_back(SC_UMIN + c); }
-        break;
-    case ALG_SCEN_STATE_BOUND:
-        if (p.ext == 1 && p.has_sb) for (int e = 0; e < 2 * p.p * p.n; e++) m.push_back(SC_EXT + e);
-        break;
-    case ALG_SCEN_WALL:
-        if (p.ext == 1) for (int w = 0; w < p.nwall; w++) for (int f = 0; f < 6; f++) m.push_back(ew + f * ALG_MAX_WALLS + w);
-        break;
-    case ALG_SCEN_CIRCLE:
-        if (p.ext == 1) for (int c = 0; c < p.ncirc; c++) for (int f = 0; f < 3; f++) m.push_back(ec + f * ALG_MAX_CIRCLES + c);
-        break;
-    case ALG_SCEN_WALL3D:
-        if (p.ext == 1) for (int w = 0; w < p.nwall3; w++) for (int f = 0; f < 12; f++) m.push_back(e3 + 12 * w + f);
-        break;
-    case ALG_SCEN_CYLINDER:       // p (3) l r of each entry; the axis (field 3) stays handle-wide
-        if (p.ext == 1) for (int c = 0; c < p.ncyl; c++) for (int f : {0, 1, 2, 4, 5}) m.push_back(ey + 6 * c + f);
-        break;
-    }
-    return m;
-}
-static bool scen_kind_ok(int kind) { return kind >= ALG_SCEN_COLLISION_RADIUS && kind <= ALG_SCEN_CYLINDER; }
 int alg_scenario_data_len(alg_handle* h, int32_t kind, int32_t* len) {
     if (!h || !len) return fail(ALG_ERR_ARG, "alg_scenario_data_len: null argument");
     if (!scen_kind_ok(kind)) return fail(ALG_ERR_ARG, "alg_scenario_data_len: unknown kind");
@@ -988,83 +1104,8 @@ int alg_get_scenario_data(alg_handle* h, int32_t kind, double* data) {
     }
     return ALG_OK;
 }
-// The rules every game's values of one kind must meet (alg_set_scenario_data; every row of alg_mpc_set_schedule): `data` = B x L values in the
-// order of `map`, `img` = the handle's shared image.  row >= 0 names the schedule row in the message.
-static int scen_validate(const Handle* hd, const char* who, int kind, const std::vector<int>& map, const std::vector<double>& img, const double* data, int row) {
-    const Params& p = hd->pr;
-    const size_t L = map.size();
-    const bool bounds = kind == ALG_SCEN_CONTROL_BOUND || kind == ALG_SCEN_STATE_BOUND;
-    for (int g = 0; g < p.B; g++) {
-        const double* v = data + (size_t)g * L;
-        auto bad = [&](const std::string& what, size_t e) {
-            return fail(ALG_ERR_ARG, std::string(who) + ": " + (row >= 0 ? "row " + std::to_string(row) + ", " : std::string()) + "game " + std::to_string(g) + ", entry " + std::to_string(e) + ": " + what);
-        };
-        for (size_t e = 0; e < L; e++) {
-            const double s0 = img[map[e]];
-            if (kind == ALG_SCEN_COLLISION_RADIUS) {
-                const int i = (int)e / p.p, j = (int)e % p.p;
-                if (i == j || !((p.ca_mask[i] >> j) & 1u)) continue;        // diagonal / pair never added: ignored
-                if (!(v[e] > 0.0) || !std::isfinite(v[e])) return bad("the radius of a pair must be positive and finite", e);
-                continue;
-            }
-            if (bounds) {
-                if (std::isfinite(s0) != std::isfinite(v[e]) || (!std::isfinite(s0) && !(s0 == v[e])))
-                    return bad("the +-inf pattern of the bounds differs from the handle's", e);
-                continue;
-            }
-            if (std::isfinite(s0) && !std::isfinite(v[e])) return bad("non-finite value where the handle's is finite", e);
-            if ((kind == ALG_SCEN_CIRCLE && e % 3 == 2) || (kind == ALG_SCEN_CYLINDER && e % 5 == 4))
-                if (!(v[e] > 0.0)) return bad("radius must be positive", e);
-        }
-        if (bounds) for (size_t e = 0; e < L / 2; e++) if (!(v[e] >= v[L / 2 + e])) return bad("Upper bounds must be greater than or equal to lower bounds", e);
-    }
-    return ALG_OK;
-}
-// alg_set_scenario_data without the bookkeeping of schedules (alg_mpc_set_schedule makes a kind per-game through it, with row 0)
-static int set_scenario_data(alg_handle* h, const char* who, int32_t kind, const double* data, bool validate) {
-    Params& p = H->pr;
-    const std::vector<int> map = scen_map(H, kind);
-    if (map.empty()) return fail(ALG_ERR_STATE, std::string(who) + ": this kind of constraint / cost was not added to the handle");
-    const size_t L = map.size(), SS = (size_t)H->scen_stride;
-    std::vector<double> img(SS);
-    scen_image(H, img.data());
-    int rc = use_device(H); if (rc) return rc;
-    if (!data) {                  // back to the shared values
-        if (!((H->scen_kinds >> kind) & 1u)) return ALG_OK;
-        H->scen_kinds &= ~(1u << kind);
-        if (!H->scen_kinds) { p.scen = H->d_scen; p.scen_stride = 0; if (p.ext == 2) p.ext = 0; return ALG_OK; }
-        for (int g = 0; g < p.B; g++) for (size_t e = 0; e < L; e++) H->scen_games[g * SS + map[e]] = img[map[e]];
-        return h2d(H, H->d_scen_games, H->scen_games.data(), sizeof(double) * SS * p.B);
-    }
-    // validation of every game before anything changes
-    if (validate && (rc = scen_validate(H, who, kind, map, img, data, -1))) return rc;
-    // the first per-game call of a base handle switches it to the EXT instantiation (multipliers re-created like every extended adder) --
-    // unless the handle was told to stay on the base kernels (alg_set_scenario_kernels): then nothing but the blocks changes, and the
-    // handle runs the twins of the base kernels that read them (ext = 2) while any kind is per game
-    const bool stay_base = p.ext != 1 && H->scen_kernels == ALG_SCEN_KERNELS_BASE;
-    if (!p.ext && !stay_base) {
-        H->keep_sched = true; rc = ext_commit(H); H->keep_sched = false;
-        if (rc) return rc;
-    }
-    if (!H->scen_kinds) {
-        if (!H->d_scen_games && (rc = dalloc(H, &H->d_scen_games, SS * p.B, "scenario blocks (per game)"))) return rc;
-        H->scen_games.resize(SS * p.B);
-        for (int g = 0; g < p.B; g++) std::copy(img.begin(), img.end(), H->scen_games.begin() + g * SS);
-    }
-    for (int g = 0; g < p.B; g++) {
-        for (size_t e = 0; e < L; e++) {
-            if (kind == ALG_SCEN_COLLISION_RADIUS) { const int i = (int)e / p.p, j = (int)e % p.p; if (i == j || !((p.ca_mask[i] >> j) & 1u)) continue; }
-            H->scen_games[g * SS + map[e]] = data[(size_t)g * L + e];
-        }
-    }
-    if ((rc = h2d(H, H->d_scen_games, H->scen_games.data(), sizeof(double) * SS * p.B))) return rc;
-    H->scen_kinds |= 1u << kind;
-    p.scen = H->d_scen_games; p.scen_stride = (int)SS;
-    if (stay_base) p.ext = 2;
-    return ALG_OK;
-}
 int alg_set_scenario_data(alg_handle* h, int32_t kind, const double* data) {
-    if (!h) return fail(ALG_ERR_ARG, "alg_set_scenario_data: null handle");
+    NEED_HANDLE("alg_set_scenario_data");
     if (!scen_kind_ok(kind)) return fail(ALG_ERR_ARG, "alg_set_scenario_data: unknown kind");
     int rc = set_scenario_data(h, "alg_set_scenario_data", kind, data, true); if (rc) return rc;
     sched_drop(H, kind);          // the caller's values replace what a schedule of this kind would apply
@@ -1375,48 +1416,6 @@ int alg_mpc_plant_advance(alg_handle* h, int32_t knot) {
     LAUNCH(k_mpc_plant_advance, H->pr, (int)knot, H->plant);
     return ALG_OK;
 }
-} // extern "C"
-// The loop of alg_mpc_solve and alg_mpc_solve_log; `who` names the entry point in the error messages
-static int mpc_solve_impl(const char* who, alg_handle* h, int32_t steps, int64_t game_id0, double* states, double* controls, alg_game_stats* stats) {
-    if (!h || steps < 1) return fail(ALG_ERR_ARG, std::string(who) + ": bad argument");
-    int rc = use_device(H); if (rc) return rc;
-    if (!H->x0_set || !H->lqr_set) return fail(ALG_ERR_STATE, std::string(who) + ": x0 / LQR data not set");
-    const Params& p = H->pr;
-    // one scratch allocation for all requested outputs: [states | controls | stats], every part 8-byte aligned; under a plant (alg_mpc_set_plant)
-    // states and controls hold one row per plant knot, steps x hold of them
-    const size_t knots = (size_t)steps * (size_t)H->plant.hold;
-    const bool planted = !mpc_plant_is_default(H->plant.hold, H->plant.substeps, H->plant.integrator);
-    const size_t b_st = states ? sizeof(double) * (knots + 1) * p.B * p.n : 0, b_uc = controls ? sizeof(double) * knots * p.B * p.m : 0,
-                 b_gs = stats ? sizeof(alg_game_stats) * (size_t)steps * p.B : 0;
-    static_assert(sizeof(alg_game_stats) % 8 == 0, "the stats log follows doubles in the scratch");
-    if (b_st + b_uc + b_gs && (rc = ensure_scratch(H, b_st + b_uc + b_gs))) return rc;
-    char* const d0 = (char*)H->d_scratch;
-    double* const d_states = states ? (double*)d0 : nullptr;
-    double* const d_controls = controls ? (double*)(d0 + b_st) : nullptr;
-    alg_game_stats* const d_stats = stats ? (alg_game_stats*)(d0 + b_st + b_uc) : nullptr;
-    bool scheduled = false;
-    for (int k = 0; k < ALG_SCHED_MAX_KINDS; k++) scheduled |= H->sched[k].rows > 0;
-    // the sibling kernels are the loop with per-step phases: a schedule, a disturbance, a log or a plant takes them
-    if (!scheduled && !H->dist.rows && !controls && !stats && !planted) rc = launch_mpc_loop(H, (int)steps, (uint64_t)game_id0, d_states);
-    else rc = launch_mpc_loop_sched(H, (int)steps, (uint64_t)game_id0, d_states, d_controls, d_stats);
-    if (rc) return rc;
-    // the loop leaves the row its last step used in the games' blocks: the host mirror of the scenario blocks follows (what the step-wise
-    // alg_set_scenario_data calls would have left; the LQR blocks have no host mirror)
-    for (int k = 0; scheduled && k < ALG_SCHED_MAX_KINDS - 1; k++) {
-        const Handle::Sched& sc = H->sched[k];
-        if (!sc.rows) continue;
-        const size_t row = (size_t)std::min((int)steps - 1, sc.rows - 1), SS = (size_t)H->scen_stride;
-        for (int g = 0; g < p.B; g++)
-            for (int e = 0; e < sc.len; e++)
-                if (sc.map[e] >= 0) H->scen_games[g * SS + sc.map[e]] = sc.data[(row * p.B + g) * sc.len + e];
-    }
-    // one copy back per output (each waits for the stream: the call is synchronous as soon as one output is asked for)
-    if (states && (rc = d2h(H, states, d_states, b_st))) return rc;
-    if (controls && (rc = d2h(H, controls, d_controls, b_uc))) return rc;
-    if (stats && (rc = d2h(H, stats, d_stats, b_gs))) return rc;
-    return ALG_OK;
-}
-extern "C" {
 int alg_mpc_solve(alg_handle* h, int32_t steps, int64_t game_id0, double* states) {
     return mpc_solve_impl("alg_mpc_solve", h, steps, game_id0, states, nullptr, nullptr);
 }
@@ -1424,25 +1423,6 @@ int alg_mpc_solve(alg_handle* h, int32_t steps, int64_t game_id0, double* states
 int alg_mpc_solve_log(alg_handle* h, int32_t steps, int64_t game_id0, double* states, double* controls, alg_game_stats* stats) {
     return mpc_solve_impl("alg_mpc_solve_log", h, steps, game_id0, states, controls, stats);
 }
-} // extern "C"
-// The plant disturbance (ALG_SCHED_DISTURBANCE): rows x B x n, needs nothing of the handle but its sizes
-static int set_disturbance(Handle* hd, int32_t rows, const double* data) {
-    int rc = use_device(hd); if (rc) return rc;
-    if (!data) { sched_drop(hd, hd->dist); return ALG_OK; }
-    if (rows < 1) return fail(ALG_ERR_ARG, "alg_mpc_set_schedule: rows must be >= 1");
-    const Params& p = hd->pr;
-    const size_t per_row = (size_t)p.B * p.n, cnt = (size_t)rows * per_row;
-    for (size_t e = 0; e < cnt; e++)
-        if (!std::isfinite(data[e])) return fail(ALG_ERR_ARG, "alg_mpc_set_schedule: row " + std::to_string(e / per_row) + ": disturbances must be finite");
-    Handle::Sched sc;
-    sc.rows = rows; sc.len = p.n;
-    if ((rc = dalloc(hd, &sc.d_data, cnt, "disturbance rows"))) return rc;
-    if ((rc = h2d(hd, sc.d_data, data, sizeof(double) * cnt))) { dfree(hd, sc.d_data); return rc; }
-    sched_drop(hd, hd->dist);
-    hd->dist = std::move(sc);
-    return ALG_OK;
-}
-extern "C" {
 // Schedules of alg_mpc_solve: per game and per MPC step values of one kind (include/algames_hip.h)
 int alg_mpc_set_schedule(alg_handle* h, int32_t kind, int32_t rows, const double* data) {
     static const char* who = "alg_mpc_set_schedule";
@@ -1450,7 +1430,7 @@ int alg_mpc_set_schedule(alg_handle* h, int32_t kind, int32_t rows, const double
     if (kind == ALG_SCHED_DISTURBANCE) return set_disturbance(H, rows, data);
     const bool target = kind == ALG_SCHED_LQR_TARGET;
     if (!target && !scen_kind_ok(kind)) return fail(ALG_ERR_ARG, "alg_mpc_set_schedule: unknown kind (an ALG_SCEN_* value, ALG_SCHED_LQR_TARGET or ALG_SCHED_DISTURBANCE)");
-    const int slot = target ? ALG_SCHED_MAX_KINDS - 1 : (int)kind;
+    const int slot = sched_slot(kind);
     int rc = use_device(H); if (rc) return rc;
     if (!data) { sched_drop(H, slot); return ALG_OK; }
     if (rows < 1) return fail(ALG_ERR_ARG, "alg_mpc_set_schedule: rows must be >= 1");
@@ -1478,7 +1458,7 @@ int alg_mpc_set_schedule(alg_handle* h, int32_t kind, int32_t rows, const double
         if (p.ext != 1 && H->scen_kernels != ALG_SCEN_KERNELS_BASE && !cfg_supported(p, 1))
             return fail(ALG_ERR_ARG, "alg_mpc_set_schedule: (model, p, d) has no compiled EXT kernel instantiation to run per-game data on");
         if (kind == ALG_SCEN_COLLISION_RADIUS)             // diagonal / pairs never added: ignored, as alg_set_scenario_data ignores them
-            for (size_t e = 0; e < map.size(); e++) { const int i = (int)e / p.p, j = (int)e % p.p; if (i == j || !((p.ca_mask[i] >> j) & 1u)) map[e] = -1; }
+            for (size_t e = 0; e < map.size(); e++) if (radius_ignored(p, e)) map[e] = -1;
     }
     // the device copies first: a failure here leaves the handle as it was
     Handle::Sched sc;
@@ -1501,7 +1481,7 @@ int alg_mpc_get_schedule(alg_handle* h, int32_t kind, int32_t* rows) {
     if (!h || !rows) return fail(ALG_ERR_ARG, "alg_mpc_get_schedule: null argument");
     if (kind == ALG_SCHED_DISTURBANCE) { *rows = H->dist.rows; return ALG_OK; }
     if (kind != ALG_SCHED_LQR_TARGET && !scen_kind_ok(kind)) return fail(ALG_ERR_ARG, "alg_mpc_get_schedule: unknown kind (an ALG_SCEN_* value, ALG_SCHED_LQR_TARGET or ALG_SCHED_DISTURBANCE)");
-    *rows = H->sched[kind == ALG_SCHED_LQR_TARGET ? ALG_SCHED_MAX_KINDS - 1 : (int)kind].rows;
+    *rows = H->sched[sched_slot(kind)].rows;
     return ALG_OK;
 }
 int alg_mpc_totals(alg_handle* h, int64_t* it, int64_t* cv, int32_t reset) {
