@@ -26,6 +26,7 @@ ALG_SCHED_LQR_TARGET = 100      # alg_mpc_set_schedule: xf (p, ni) | uf (p, mi) 
 ALG_SCHED_DISTURBANCE = 101     # alg_mpc_set_schedule: w (n) per MPC step and game, added to the advanced state
 ALG_PLANT_RK2, ALG_PLANT_RK4 = 0, 1    # alg_mpc_set_plant: the plant's integrator
 PLANT_INTEGRATORS = ("rk2", "rk4")
+ALG_KKT_RHS_USER, ALG_KKT_RHS_X0, ALG_KKT_RHS_XF = 0, 1, 2    # alg_kkt_solve: the right-hand sides' kind
 SCEN_KINDS = ("collision_radius", "collision_cost", "control_bound", "state_bound", "wall", "circle", "wall3d", "cylinder")
 
 
@@ -136,6 +137,7 @@ SIGNATURES = {
     "release_scratch": (C.c_int, [_P]),
     "get_violation_profile": (C.c_int, [_P, _D, _D, _D, _D]),
     "newton_direction": (C.c_int, [_P, C.c_double, _D, _I]),
+    "kkt_solve": (C.c_int, [_P, C.c_double, C.c_int32, C.c_int32, _D, C.c_int32, C.c_int32, _D, _I]),
     "line_search": (C.c_int, [_P, C.c_double, _D, _D, _I]),
     "update_traj": (C.c_int, [_P, C.c_int32, C.c_int32, _D]),
     "record_stats": (C.c_int, [_P, _P]),
@@ -168,7 +170,7 @@ SIGNATURES = {
 # Entry points a backend may lack (the CPU oracle has no per-game scenario data): bound when present; calling one that is absent
 # raises AlgamesError naming the backend.
 OPTIONAL = frozenset({"scenario_data_len", "set_scenario_data", "get_scenario_data", "set_scenario_kernels", "get_scenario_kernels",
-                      "mpc_set_schedule", "mpc_get_schedule", "mpc_solve_log", "mpc_set_plant", "mpc_get_plant", "mpc_plant_advance"})
+                      "mpc_set_schedule", "mpc_get_schedule", "mpc_solve_log", "mpc_set_plant", "mpc_get_plant", "mpc_plant_advance", "kkt_solve"})
 
 
 class AlgamesError(RuntimeError):
@@ -573,6 +575,35 @@ class Batch:
         delta = np.empty((self.B, self.S)); st = np.empty(self.B, dtype=np.int32)
         self.lib.check(self.lib.newton_direction(self.h, reg, _dptr(delta), _iptr(st)))
         return delta, st
+
+    def kkt_solve(self, rhs=None, kind="user", reg=0.0, games=None):
+        """J X = R at the current iterate (alg_kkt_solve): J is the residual Jacobian of residual_jacobian(reg) at pdtraj, solved on the device
+        by the structured elimination of newton_direction (refinement gate included), one elimination per column.
+        kind = "user": rhs[cnt, nrhs, S] (or [cnt, S]: one column) in the VERTICAL order of residual(); rhs = -res gives the Newton direction.
+        kind = "x0":   R = -d res / d x_1, n columns: X = d z* / d x0.     kind = "xf": R = -d res / d x_f, p ni columns in the xf order of set_lqr.
+        The derivative is that of the root of res(z; theta) = 0 with the multipliers and penalties held; exact for the double integrator, the
+        Gauss-Newton sensitivity of the reference's Jacobian (no second-order dynamics terms) for the other models; reg != 0 solves the
+        regularised system.  games = (first, count).  Returns (X[cnt, nrhs, S] in horizontal order, status[cnt])."""
+        first, cnt = (0, self.B) if games is None else (int(games[0]), int(games[1]))
+        code = {"user": ALG_KKT_RHS_USER, "x0": ALG_KKT_RHS_X0, "xf": ALG_KKT_RHS_XF}.get(kind, kind)
+        if code not in (ALG_KKT_RHS_USER, ALG_KKT_RHS_X0, ALG_KKT_RHS_XF):
+            raise ValueError(f"unknown right-hand-side kind {kind!r}: 'user', 'x0' or 'xf'")
+        if code == ALG_KKT_RHS_USER:
+            if rhs is None:
+                raise ValueError("kind='user' needs rhs")
+            r = np.asarray(rhs, dtype=np.float64)
+            if r.ndim == 2:
+                r = r[:, None, :]
+            if r.ndim != 3 or r.shape[0] != cnt or r.shape[1] < 1 or r.shape[2] != self.S:
+                raise ValueError(f"expected shape {(cnt, 'nrhs', self.S)}, got {tuple(np.shape(rhs))}")
+            r = _f64(r, r.shape); nrhs = r.shape[1]
+        else:
+            if rhs is not None:
+                raise ValueError("rhs is only taken with kind='user'")
+            r = None; nrhs = self.n if code == ALG_KKT_RHS_X0 else self.p * self.ni
+        X = np.empty((max(cnt, 0), nrhs, self.S)); st = np.empty(max(cnt, 0), dtype=np.int32)
+        self.lib.check(self.lib.kkt_solve(self.h, float(reg), code, nrhs, _dptr(r), first, cnt, _dptr(X), _iptr(st)))
+        return X, st
 
     def line_search(self, res_norm, reg=0.0):
         rn = _f64(res_norm, (self.B,)); a = np.empty(self.B); j = np.empty(self.B, dtype=np.int32)

@@ -13,8 +13,9 @@
 // every kernel instantiation lives in its own translation unit: the base configurations in algames_base.hip (compiled once per
 // entry; algames_base_scen.hip / algames_mw_scen.hip: their twins that read the game's scenario block), the EXT instantiations in
 // algames_ext_*.hip, the team kernels in algames_mw.hip, the dense-direction ones in theirs, the scheduled receding-horizon loops in algames_sched.hip
-// (a one-wavefront configuration has its kernels, its scheduled loop and its plant knot, a team its kernels and its scheduled loop)
-#define ALG_DECLARE_ONE_(M, P, D, E) ALG_DECLARE_KERNELS(M, P, D, E) ALG_DECLARE_SCHED(M, P, D, E) ALG_DECLARE_PLANT(M, P, D, E)
+// (a one-wavefront configuration has its kernels, its scheduled loop, its plant knot and its KKT solve -- algames_kkt.hip --, a team its kernels
+// and its scheduled loop)
+#define ALG_DECLARE_ONE_(M, P, D, E) ALG_DECLARE_KERNELS(M, P, D, E) ALG_DECLARE_SCHED(M, P, D, E) ALG_DECLARE_PLANT(M, P, D, E) ALG_DECLARE_KKT(M, P, D, E)
 #define ALG_DECLARE_TEAM_(M, P, D, E, W) ALG_DECLARE_MW(M, P, D, E, W) ALG_DECLARE_SCHED_MW(M, P, D, E, W)
 ALG_CFGS_BASE(ALG_DECLARE_ONE_)
 ALG_CFGS_BASE_SCEN(ALG_DECLARE_ONE_)
@@ -1231,6 +1232,36 @@ int alg_newton_direction(alg_handle* h, double reg, double* delta, int32_t* stat
     // strip the x_1 slot: delta is B x S in horizontal order
     if (delta && (rc = d2h_seg(H, delta, zseg(H, 2) + p.n, p.stride, sizeof(double) * p.S))) return rc;
     return sync(H);
+}
+
+// J X = R for many right-hand sides (k_kkt_solve): [rhs | out | status] in the inspection scratch, one upload, one launch, one download
+int alg_kkt_solve(alg_handle* h, double reg, int32_t kind, int32_t nrhs, const double* rhs, int32_t first_game, int32_t n_games, double* out, int32_t* status) {
+    NEED_HANDLE("alg_kkt_solve");
+    const Params& p = H->pr;
+    if (kind != ALG_KKT_RHS_USER && kind != ALG_KKT_RHS_X0 && kind != ALG_KKT_RHS_XF) return fail(ALG_ERR_ARG, "alg_kkt_solve: kind must be ALG_KKT_RHS_USER, ALG_KKT_RHS_X0 or ALG_KKT_RHS_XF");
+    if (!out) return fail(ALG_ERR_ARG, "alg_kkt_solve: null out");
+    if (first_game < 0 || n_games < 1 || (long long)first_game + n_games > p.B) return fail(ALG_ERR_ARG, "alg_kkt_solve: game range outside the batch");
+    const bool user = kind == ALG_KKT_RHS_USER;
+    if (user) {
+        if (nrhs < 1) return fail(ALG_ERR_ARG, "alg_kkt_solve: ALG_KKT_RHS_USER needs nrhs >= 1");
+        if (!rhs) return fail(ALG_ERR_ARG, "alg_kkt_solve: ALG_KKT_RHS_USER needs rhs");
+    } else {
+        const int all = kind == ALG_KKT_RHS_X0 ? p.n : p.p * p.ni;
+        if (nrhs != 0 && nrhs != all) return fail(ALG_ERR_ARG, "alg_kkt_solve: nrhs must be n (ALG_KKT_RHS_X0) / p ni (ALG_KKT_RHS_XF), or 0 for all");
+        if (rhs) return fail(ALG_ERR_ARG, "alg_kkt_solve: rhs must be NULL unless ALG_KKT_RHS_USER");
+        nrhs = all;
+    }
+    const size_t cnt = (size_t)n_games * (size_t)nrhs * (size_t)p.S, b_col = sizeof(double) * cnt, b_rhs = user ? b_col : 0;
+    if (user) for (size_t e = 0; e < cnt; e++) if (!std::isfinite(rhs[e])) return fail(ALG_ERR_ARG, "alg_kkt_solve: game " + std::to_string(first_game + e / ((size_t)nrhs * p.S)) + ", column " + std::to_string(e / p.S % nrhs) + ": rhs must be finite");
+    int rc = use_device(H); if (rc) return rc;
+    if ((rc = ensure_scratch(H, b_rhs + b_col + sizeof(int) * (size_t)n_games))) return rc;
+    char* const d = (char*)H->d_scratch;
+    if (user && (rc = h2d(H, d, rhs, b_rhs))) return rc;
+    LAUNCH_GRID(n_games, k_kkt_solve, H->pr, reg, (int)kind, (int)nrhs, (const double*)(user ? d : nullptr), (int)first_game, (double*)(d + b_rhs), (int*)(d + b_rhs + b_col));
+    // (the columns come back in one copy; the status words, n_games ints behind them, go to a host buffer of their own)
+    if ((rc = d2h(H, out, d + b_rhs, b_col))) return rc;
+    if (status && (rc = d2h(H, status, d + b_rhs + b_col, sizeof(int) * (size_t)n_games))) return rc;
+    return ALG_OK;
 }
 
 int alg_line_search(alg_handle* h, double reg, const double* rn, double* alpha, int32_t* j) {

@@ -960,6 +960,76 @@ def residual_jacobian(prob, reg=0.0, games=None):
     return prob.batch.residual_jacobian(reg, games)
 
 
+class EquilibriumSensitivity:
+    """d z* / d theta of a batch of games: `dz` is (cnt, S, q) in the horizontal order of Δtraj (rows) by the q entries of theta (columns);
+    `status` (cnt,) is the per-game status of the solves (0 = every column solved).  The accessors slice rows by the index maps of
+    horizontal_indices: knots and steps are 1-based like the reference's stamps."""
+
+    def __init__(self, dz, status, wrt, N, n, p, mi):
+        self.dz, self.status, self.wrt = dz, status, wrt
+        self.N, self.n, self.p, self.mi = N, n, p, mi
+        self._b = n + p * mi + p * n
+
+    def dx(self, k):
+        """d x_k / d theta, (cnt, n, q), knots k = 2 ... N (x_1 is the initial state itself)."""
+        if not 2 <= k <= self.N:
+            raise IndexError(f"state knot {k}: 2 ... {self.N}")
+        o = (k - 2) * self._b
+        return self.dz[:, o:o + self.n, :]
+
+    def du(self, k, i=None):
+        """d u_k / d theta, steps k = 1 ... N - 1: (cnt, m, q) in the stored order of get_traj (player by player), or player i's (cnt, mi, q)."""
+        if not 1 <= k <= self.N - 1:
+            raise IndexError(f"control step {k}: 1 ... {self.N - 1}")
+        o = (k - 1) * self._b + self.n
+        if i is None:
+            return self.dz[:, o:o + self.p * self.mi, :]
+        if not 1 <= i <= self.p:
+            raise IndexError(f"player {i}: 1 ... {self.p}")
+        return self.dz[:, o + (i - 1) * self.mi:o + i * self.mi, :]
+
+    def dλ(self, k, i):
+        """d lambda_{i,k} / d theta (player i's multiplier of the dynamics of step k = 1 ... N - 1), (cnt, n, q)."""
+        if not 1 <= k <= self.N - 1 or not 1 <= i <= self.p:
+            raise IndexError(f"multiplier (player {i}, step {k}): players 1 ... {self.p}, steps 1 ... {self.N - 1}")
+        o = (k - 1) * self._b + self.n + self.p * self.mi + (i - 1) * self.n
+        return self.dz[:, o:o + self.n, :]
+
+    dlam = dλ
+
+
+def kkt_solve(prob, rhs=None, kind="user", reg=0.0, games=None):
+    """J X = R at pdtraj on the device (Batch.kkt_solve): X (cnt, nrhs, S) in horizontal order and the per-game status."""
+    prob._sync_options()
+    return prob.batch.kkt_solve(rhs, kind, reg, games)
+
+
+def equilibrium_sensitivity(prob, wrt="x0", reg=0.0, games=None):
+    """How the equilibrium at pdtraj moves with the problem: d z* / d theta = -J^-1 d res / d theta for theta = the initial state (wrt = "x0",
+    q = n columns) or the players' LQR targets x_f (wrt = "xf", q = p ni columns in the xf order of set_lqr), solved on the device in one
+    launch (alg_kkt_solve).  Returns an EquilibriumSensitivity; `.dz` is (cnt, S, q) in horizontal order.
+
+    Meaning: the derivative of the root z*(theta) of res(z; theta) = 0 -- the system newton_solve solves in its inner loop -- with the
+    multipliers lambda and penalties mu of the constraints (and the active sets behind them) HELD at their current values.  J is the
+    reference's residual Jacobian, which drops the second-order terms of the dynamics (global_quantities.jl:150-172): the result is exact
+    for the double integrator (linear dynamics) and the Gauss-Newton sensitivity of that Jacobian for the unicycle, bicycle and quadrotor.
+    A non-zero `reg` solves the regularised system (regularize_residual_jacobian!) instead.  Call it on a solved problem: away from a root the
+    linearisation is still that of the current iterate.  games = (first, count)."""
+    if wrt not in ("x0", "xf"):
+        raise ValueError(f"wrt must be 'x0' or 'xf', got {wrt!r}")
+    prob._sync_options()
+    b = prob.batch
+    X, st = b.kkt_solve(None, wrt, reg, games)
+    return EquilibriumSensitivity(np.ascontiguousarray(X.transpose(0, 2, 1)), st, wrt, b.N, b.n, b.p, b.mi)
+
+
+def feedback_gains(prob, games=None):
+    """The local feedback policy around the plan at pdtraj: d u_1 / d x0, (cnt, m, n), rows in the stored order of get_traj (the order of the
+    `controls` log of mpc_rollout), columns the entries of the initial state.  u_1(x0 + e) = u_1 + K e to first order, with multipliers and
+    penalties held; exact for the double integrator, Gauss-Newton for the other models (equilibrium_sensitivity)."""
+    return np.ascontiguousarray(equilibrium_sensitivity(prob, "x0", 0.0, games).du(1))
+
+
 def inner_iteration(prob, LS_count, t_elap, Δ, k, l):
     """inner_iteration(prob, LS_count, t_elap, Δ, k, l) (solver_methods.jl:67-103).
     Returns (LS_count (B,), control_flow (B,) of 'continue'/'break', Δ (B,), info)."""

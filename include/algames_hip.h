@@ -371,6 +371,31 @@ int alg_release_scratch(alg_handle* h);
 int alg_get_violation_profile(alg_handle* h, double* dyn, double* con, double* sta, double* opt);
 /* Δtraj = -lu(jac) \ res ; set_traj!(Δpdtraj, Δtraj) (solver_methods.jl:87-88).  delta: B x S or NULL. */
 int alg_newton_direction(alg_handle* h, double reg, double* delta, int32_t* status /*B or NULL*/);
+/* KKT solves with many right-hand sides at the current iterate: J X = R with J the (regularised) residual Jacobian of
+ * alg_residual_jacobian(reg) at pdtraj, solved on the device by the structured elimination of alg_newton_direction, refinement
+ * gate included (alg_set_refinement); one launch, one assemble pass per game, one elimination per column.
+ *   kind = ALG_KKT_RHS_USER: rhs holds n_games x nrhs columns of S doubles in the VERTICAL order of alg_residual; nrhs >= 1.
+ *                            rhs = -res gives the Newton direction.
+ *   kind = ALG_KKT_RHS_X0:   R = -d res / d x_1 (x_1 = the initial state x0), n columns: X = d z* / d x0, the sensitivity of the root
+ *                            of res(z; x0) = 0 to the initial state.
+ *   kind = ALG_KKT_RHS_XF:   R = -d res / d x_f, p ni columns in the xf order of alg_set_lqr: X = d z* / d x_f.
+ *   For X0 / XF rhs must be NULL and nrhs the full count or 0 ("all").
+ * The derivatives hold the multipliers and penalties (and the active sets behind them) fixed.  J is the reference's Jacobian
+ * (global_quantities.jl:109-193), which drops the second-order terms of the dynamics: the sensitivities are exact for the
+ * DoubleIntegrator (linear dynamics) and Gauss-Newton sensitivities for the other models.  reg != 0 solves the regularised system.
+ * out: n_games x nrhs x S, every column in the HORIZONTAL order of alg_newton_direction's delta.  status: n_games entries or NULL, per
+ * game the first status other than ALG_STATUS_OK among its columns.
+ * ALG_ERR_ARG, with nothing changed, for an unknown kind, a bad count, a null or non-finite rhs (USER), a non-null rhs (X0 / XF), a
+ * null out, or a game range outside the batch.
+ * What the call leaves behind: pdtraj, x0, multipliers, penalties, statistics (`refinements` included) and the history are untouched;
+ * ALG_TRAJ_DELTA of every game in the range holds its last column; ALG_TRAJ_TRIAL is scratch (x_1 restored); the
+ * step records and the direction-gate figures (alg_get_direction_gate) are rewritten -- every solver entry point reassembles the records
+ * before it reads them.  Uses the inspection scratch (alg_release_scratch). */
+#define ALG_KKT_RHS_USER 0
+#define ALG_KKT_RHS_X0   1
+#define ALG_KKT_RHS_XF   2
+int alg_kkt_solve(alg_handle* h, double reg, int32_t kind, int32_t nrhs, const double* rhs /* n_games x nrhs x S, vertical order; NULL unless USER */,
+                  int32_t first_game, int32_t n_games, double* out /* n_games x nrhs x S, horizontal order */, int32_t* status /* n_games or NULL */);
 /* line_search (solver_methods.jl:105-125) on the stored Δpdtraj. */
 int alg_line_search(alg_handle* h, double reg, const double* res_norm /*B*/, double* alpha /*B*/,
                     int32_t* j /*B*/);
