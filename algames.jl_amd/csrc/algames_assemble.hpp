@@ -4,44 +4,6 @@
 #pragma once
 #include "algames_device.hpp"
 
-// Round-6 A/B switches of the fused pass (tests/probes/build_variant.sh; 1 = shipped)
-#ifndef ALG_R6_ROWIDX
-#define ALG_R6_ROWIDX 1           // fused pass, rows opt_x: (step, entry) of a row carried from trip to trip
-#endif
-#ifndef ALG_R6_LANEROLE
-#define ALG_R6_LANEROLE 1         // fused pass, double integrator: a lane keeps its row of the step for the whole chunk, the trips walk the steps (2: the staging too)
-#endif
-#ifndef ALG_LSM_DI1W
-#define ALG_LSM_DI1W 0            // (documented at LsMulti below)
-#endif
-#ifndef ALG_R6_LANEROLE_UNI
-#define ALG_R6_LANEROLE_UNI 0     // ... the one-wavefront unicycle kernels too (the line search's group pass then deals its rows the same way: bit-identical to the
-                                  // fused pass, tests green).  Measured and NOT taken (profiles/r06_ab_lru_*.txt): C5 at 4096 / 1024 games + 0.6 / + 0.8 %, C3 at 4096
-                                  // games (P n = 64: the flat dealing wastes no lane there) - 2.5 %, and the receding-horizon loop at 4096 seeds 3.83 -> 3.16 M/s --
-                                  // another rounding of the norms, other closed-loop trajectories, a slower straggler
-#endif
-#ifndef ALG_R6_STAGE
-#define ALG_R6_STAGE 1      // every global load of a chunk in flight before the first wait
-#endif
-#ifndef ALG_R6_STAGE_BATCH
-#define ALG_R6_STAGE_BATCH 6    // ... elements of z and dz per lane and batch in the 128-register kernels
-#endif
-#ifndef ALG_R6_STAGE_BATCH_REC
-#define ALG_R6_STAGE_BATCH_REC 6 // ... elements of z per lane and batch in the record pass of the 128-register kernels (no dz; all twelve in one batch measured: neutral, profiles/r06_ab_rec12_c2.txt)
-#endif
-#ifndef ALG_R6_STAGE_BATCH_LR
-#define ALG_R6_STAGE_BATCH_LR 4 // ... blocks per batch of the lane-role staging
-#endif
-#ifndef ALG_R6_STAGE_BATCH_W2
-#define ALG_R6_STAGE_BATCH_W2 10   // ... in the 256-register kernels (the 4-player unicycle's chunk is 20 elements per lane: 40 doubles in flight at once spilled its loop kernel)
-#endif
-#ifndef ALG_R6_PHASEA_CHUNK
-#define ALG_R6_PHASEA_CHUNK 1   // fused pass: phase A per chunk out of the staged blocks, pair-gradient tables straight into the chunk's LDS (no global round trip)
-#endif
-#ifndef ALG_R6_PHASEA
-#define ALG_R6_PHASEA 1     // phase A: multipliers / penalties of an item's pairs requested together with its positions; LDS-only fences between the staged write-outs
-#endif
-
 namespace alg {
 
 // ================================================================================================
@@ -77,10 +39,9 @@ template <class C> __device__ __forceinline__ void team_combine(ResOut& o) {
     }
 }
 
-// rows of the fused pass dealt as (step, row of the step) = (trip, lane): see assemble_fused.  The group pass of the line search (trial_norms_multi) on a
-// one-wavefront kernel must sum its rows per lane in the order of the fused pass (bit-identical norms): it follows this switch.
-template <class C> inline constexpr bool lane_roles_v = ALG_R6_LANEROLE != 0 && AsmLds<C>::FUSED && C::P * C::n <= C::NT &&
-    ((C::MODEL == ALG_MODEL_DOUBLE_INTEGRATOR && !ALG_LSM_DI1W) || (ALG_R6_LANEROLE_UNI != 0 && C::MODEL == ALG_MODEL_UNICYCLE));
+// rows of the fused pass dealt as (step, row of the step) = (trip, lane): see assemble_fused.  (The group pass of the line search -- trial_norms_multi -- on a
+// one-wavefront kernel must sum its rows per lane in the order of the fused pass: it runs on the unicycle kernels only, which keep the flat dealing.)
+template <class C> inline constexpr bool lane_roles_v = AsmLds<C>::FUSED && C::P * C::n <= C::NT && C::MODEL == ALG_MODEL_DOUBLE_INTEGRATOR;
 struct AsmAcc { double l1 = 0, l1r = 0, l1f = 0, vopt = 0, vdyn = 0, vcon = 0, vsta = 0; int bad = 0; };
 // Roundings of the pair terms, stated once.  Phase A of the assemble pass, phase A of the line search's group pass (trial_norms_multi) and
 // dual_penalty_update evaluate the same pair expressions, and the group pass's norms must equal the ordinary pass's bit for bit: wherever a
@@ -121,6 +82,12 @@ __device__ __forceinline__ double scen_player(CPR pr, const Game& G, const ALG_A
 // (i, j), the extended set's wall / circle terms -- shared by the pass over all steps (assemble_phase_a) and the per-chunk form of the fused pass
 // (round 6).  xp(idx): entry idx of x_{k+1} of the (trial) iterate; lmu(jj, ci, lam, mu): multiplier and penalty of constraint row ci (pair jj);
 // rec: the step's record head [.. Hh | Hd ..] (or its staging slot), tab: the step's pair-gradient table.
+// DUAL: the pass is the record! of the fused pass that follows dual_update! + penalty_update! (solver_methods.jl:57-61 then :73): both stream the same
+// iterate and the same multipliers, so the item that evaluates a collision-avoidance row also updates its lambda and mu -- in registers,
+// with dual_penalty_update's expressions -- stores them together with the constraint value (evaluate!), and forms the augmented-Lagrangian
+// terms with the new values.  One pass instead of two per outer iteration.
+// (DUAL is the compile-time capability -- the record! instantiation of the fused pass -- and `dual` the wave-uniform request of this call: the
+// solver kernel holds ONE record! instantiation, not two)
 template <class C, int MODE, bool IBR, bool DUAL, class XP, class LMU>
 __device__ __forceinline__ void phase_a_pos_item(CPR pr, const Game& G, int N, int k, int i, int ip, double dt, bool pairs_on, XP&& xp, LMU&& lmu,
                                                  double* __restrict__ rec, double* __restrict__ tab, AsmAcc& acc, bool dual) {
@@ -134,7 +101,6 @@ __device__ __forceinline__ void phase_a_pos_item(CPR pr, const Game& G, int N, i
         for (int a = 0; a < PD; a++) { xi[a] = xp(a * P + i); ga[a] = 0.0; }
 #pragma unroll
         for (int t = 0; t < NS; t++) dd[t] = 0.0;
-#if ALG_R6_PHASEA
         // Round 6: everything an item reads from global memory is requested before its arithmetic starts -- the positions of the other
         // players and the multiplier / penalty of every pair (they sat behind the sqrt / division chains of the pair before: one exposed
         // round trip per pair) -- and the per-player constants come from scalar loads (sel_player).
@@ -153,7 +119,6 @@ __device__ __forceinline__ void phase_a_pos_item(CPR pr, const Game& G, int N, i
         const double cc_mu_i = pr.has_colcost ? scen_player<C, P>(pr, G, pr.cc_mu, SC_CCM, i, [](int q) { return q; }) : 0.0;
         const double cc_rad_i = pr.has_colcost ? scen_player<C, P>(pr, G, pr.cc_radius, SC_CCR, i, [](int q) { return q; }) : 0.0;
         const unsigned ca_mask_i = sel_player<P>(pr.ca_mask, i, [](int q) { return q; });
-#endif
 #pragma unroll
         for (int jj = 0; jj < P - 1; jj++) {
             const int j = jj < i ? jj : jj + 1;
@@ -164,21 +129,12 @@ __device__ __forceinline__ void phase_a_pos_item(CPR pr, const Game& G, int N, i
             for (int t = 0; t < NS; t++) H[t] = 0.0;
             if (pairs_on) {
                 double dl[PD];
-#if ALG_R6_PHASEA
 #pragma unroll
                 for (int a = 0; a < PD; a++) dl[a] = xi[a] - xj[jj][a];
-#else
-#pragma unroll
-                for (int a = 0; a < PD; a++) dl[a] = xi[a] - xp(a * P + j);
-#endif
                 const double dl0 = dl[0], dl1 = dl[1];
                 const double s2 = pair_dist2(dl0, dl1);
                 if (pr.has_colcost) {                                    // CollisionCost, objective.jl:134-173 (planar: px[i])
-#if ALG_R6_PHASEA
                     const double nrm = sqrt(s2), mu = cc_mu_i, rad = cc_rad_i;
-#else
-                    const double nrm = sqrt(s2), mu = ALG_SCEN_AT(C, pr, G, cc_mu, SC_CCM, i), rad = ALG_SCEN_AT(C, pr, G, cc_radius, SC_CCR, i);
-#endif
                     if (fmax(0.0, rad - nrm) > 0.0) {
                         const double eps = 1e-10, eps_norm = eps * sqrt((double)n);
                         const double g0 = mu * (rad * (eps + dl0) / (eps_norm + nrm) - dl0);
@@ -191,30 +147,17 @@ __device__ __forceinline__ void phase_a_pos_item(CPR pr, const Game& G, int N, i
                     }
                 }
                 if (pr.has_colavoid) {                                   // CollisionConstraint + AL expansion
-#if ALG_R6_PHASEA
                     const double Rr = scen_player<C, P>(pr, G, pr.ca_pair_r, SC_CAR, i, [jj](int q) { return q * MAXP + (jj < q ? jj : jj + 1); });
                     const double on = (double)((ca_mask_i >> j) & 1u);                        // 0: this ordered pair carries no constraint
-#else
-                    const double Rr = ALG_SCEN_AT(C, pr, G, ca_pair_r, SC_CAR, i * MAXP + j);
-                    const double on = (double)((pr.ca_mask[i] >> j) & 1u);                    // 0: this ordered pair carries no constraint
-#endif
                     double s2c = s2;
                     if constexpr (PD == 3) { if (pr.ca_dim != 3) dl[2] = 0.0; s2c = __builtin_fma(dl[2], dl[2], s2c); }   // spherical: pz[i][1:3]
                     const double c = ca_value(on, Rr, s2c);
                     const int ci = con_col<C>(N, pairq<C>(i, j), kn);
-#if ALG_R6_PHASEA
                     double lm = lmq[jj], mu_c = muq[jj];
-#else
-                    double lm = gld(G.lam(pr), ci), mu_c = gld(G.mu(pr), ci);
-#endif
                     if (DUAL && dual) {
                         // dual_update! with alphax_dual[i], then penalty_update! (constraints_methods.jl:421-440, 329-379): dual_penalty_update's expressions
                         const auto& od = pr.opt;
-#if ALG_R6_PHASEA
                         const double ax = sel_player<P>(od.alphax_dual, i, [](int q) { return q; });
-#else
-                        const double ax = od.alphax_dual[i];
-#endif
                         lm = dual_ascent(lm, ax, mu_c, c, od.lambda_max);
                         mu_c = fmin(fmax(mu_c * od.rho_increase, 0.0), od.rho_max);
                         gst(G.lam(pr), ci, lm); gst(G.mu(pr), ci, mu_c); gst(G.vals(pr), ci, c);
@@ -290,16 +233,11 @@ __device__ __forceinline__ void phase_a_pos_item(CPR pr, const Game& G, int N, i
 }
 
 // Phase A of the assemble pass (see assemble_pass): RK2 Jacobian coefficients and the pair / wall / circle terms of every (knot, player).
-// dzp != nullptr: the positions are those of the trial iterate z + alpha dz, formed on the fly (fused trial pass of the double integrator).
-// DUAL (round 6): the pass is the record! that follows dual_update! + penalty_update! (solver_methods.jl:57-61 then :73): both stream the same
-// iterate and the same multipliers, so the item that evaluates a collision-avoidance row also updates its lambda and mu -- in registers,
-// with dual_penalty_update's expressions -- stores them together with the constraint value (evaluate!), and forms the augmented-Lagrangian
-// terms with the new values.  One pass instead of two per outer iteration.
-// (DUAL is the compile-time capability -- the record! instantiation of the fused pass -- and `dual` the wave-uniform request of this call: the
-// solver kernel holds ONE record! instantiation, not two)
-template <class C, int MODE, bool IBR, bool DUAL = false>
-__device__ __forceinline__ void assemble_phase_a(CPR pr, const Game& G, AsmLds<C>& L, const double* __restrict__ z, const double* __restrict__ dzp, double alpha,
-                                                 int N, int lane, double dt, int ip, AsmAcc& acc, bool dual = false) {
+// dzp != nullptr: the positions are those of the trial iterate z + alpha dz, formed on the fly.  (No caller passes it any more -- the fused pass runs
+// its phase A per chunk, assemble_fused -- but without the parameter the pass compiles to other, equivalent, machine code: it stays until a change
+// that is allowed to move instructions.)
+template <class C, int MODE, bool IBR>
+__device__ __forceinline__ void assemble_phase_a(CPR pr, const Game& G, AsmLds<C>& L, const double* __restrict__ z, const double* __restrict__ dzp, double alpha, int N, int lane, double dt, int ip, AsmAcc& acc) {
     constexpr int n = C::n, P = C::P;
     using R = Rec<C>;
     constexpr bool RECS = (MODE == 1 || MODE == 2 || MODE == 3);
@@ -320,7 +258,7 @@ __device__ __forceinline__ void assemble_phase_a(CPR pr, const Game& G, AsmLds<C
 #pragma unroll
                 for (int t = 0; t < 10; t++) rec[R::COEF + t * P + i] = cf[t];
             } else if constexpr (C::MODEL == ALG_MODEL_UNICYCLE) {
-                // Jacobian coefficients of knot k (A_k, B_k): see the model section (of the trial iterate when dzp is given)
+                // Jacobian coefficients of knot k (A_k, B_k): see the model section
                 const double* sk = zstate<C>(z, k); const double* dk = (dzp && k > 0) ? zstate<C>(dzp, k) : nullptr;      // (x_1 does not move)
                 const int uo_ = n + hu<C>(k, i);
                 auto sv = [&](int idx) { const double q = sk[idx]; return dk ? __builtin_fma(alpha, dk[idx], q) : q; };      // (update_traj!'s fma: the value the trial buffer holds)
@@ -336,13 +274,13 @@ __device__ __forceinline__ void assemble_phase_a(CPR pr, const Game& G, AsmLds<C
                 const double* x1 = z + n + hx<C>(k); const double* d1 = dzp ? dzp + n + hx<C>(k) : nullptr;
                 auto xp = [&](int idx) { const double v = gld(x1, idx); return d1 ? __builtin_fma(alpha, gld(d1, idx), v) : v; };    // position of the (trial) iterate: update_traj!'s fma
                 auto lmu = [&](int, int ci, double& lm, double& mu_c) { lm = gld(G.lam(pr), ci); mu_c = gld(G.mu(pr), ci); };
-                phase_a_pos_item<C, MODE, IBR, DUAL>(pr, G, N, k, i, ip, dt, pairs_on, xp, lmu, rec, tab, acc, dual);
+                phase_a_pos_item<C, MODE, IBR, false>(pr, G, N, k, i, ip, dt, pairs_on, xp, lmu, rec, tab, acc, false);
             }
           }
           if constexpr (STAGED) {
-              // (round 6: the two fences around the write-out order LDS only -- the staging slots are what they protect; the global stores
+              // (the two fences around the write-out order LDS only -- the staging slots are what they protect; the global stores
               // are waited for once, behind the loop)
-              if constexpr (ALG_R6_PHASEA != 0) sweep_sync<C>(); else game_sync();
+              sweep_sync<C>();
               // write-out: contiguous [coef | Hh | Hd] and table segments of the staged steps
               const int nst = (N - 1 - kA) < SPP ? (N - 1 - kA) : SPP;
               for (int t = lane; t < nst * SL; t += C::NT) {
@@ -351,10 +289,10 @@ __device__ __forceinline__ void assemble_phase_a(CPR pr, const Game& G, AsmLds<C
                   if (o >= HEAD) G.rec(pr)[R::gvt(N, kA + ks2) + (o - HEAD)] = L.stage[t];
                   else if (RECS || o < C::NC) G.rec(pr)[base + o] = L.stage[t];
               }
-              if constexpr (ALG_R6_PHASEA != 0) sweep_sync<C>(); else game_sync();
+              sweep_sync<C>();
           }
         }
-        if constexpr (!AsmLds<C>::STAGED || ALG_R6_PHASEA != 0) game_sync();
+        game_sync();
     }
 }
 
@@ -595,7 +533,7 @@ __device__ void assemble_pass(CPR pr0, const Game& G0, AsmLds<C>& L, int zsel, i
 //   MODE 0 / 3 as in assemble_pass (3 = statistics and records of the unregularised rows + the regularised norm l1reg)
 // Same row arithmetic as assemble_pass (same expressions in the same order); the norms are summed in another order.
 // ================================================================================================
-//   DUAL (record! only): the pass also performs the dual_update! + penalty_update! that precede it in newton_solve! (see assemble_phase_a)
+//   DUAL (record! only): the pass also performs the dual_update! + penalty_update! that precede it in newton_solve! (see phase_a_pos_item)
 template <class C, int MODE, bool AXPY, bool DUAL = false>
 __device__ void assemble_fused(CPR pr0, const Game& G0, AsmLds<C>& L, double alpha, bool prox, double reg, double jreg, ResOut& out, bool dual = false) {
     static_assert(AsmLds<C>::FUSED && (MODE == 0 || MODE == 1 || MODE == 3), "fused trial pass: double integrator / unicycle, statistics / record modes");
@@ -615,13 +553,12 @@ __device__ void assemble_fused(CPR pr0, const Game& G0, AsmLds<C>& L, double alp
     double* __restrict__ zo = G.z(1);                          // the trial iterate goes here
     AsmAcc acc;
     LSP_T0 LSP_COUNT(25)
-    // ---- phase A over all steps (positions of the trial iterate formed on the fly), heads and tables to the records as in assemble_pass
-    // Round 6 (PCH): phase A runs per chunk, out of the staged blocks -- the positions of iterate and direction are not read a second time from
+    // PCH: phase A runs per chunk, out of the staged blocks -- the positions of iterate and direction are not read a second time from
     // global memory, the pair-gradient tables never leave the chunk's LDS, the Jacobian coefficients of the unicycle go straight to the chunk
     // (and to the records for the sweeps), the record heads [Hh | Hd] are stored by the items themselves.  One item per lane: (step, player).
-    constexpr bool PCH = ALG_R6_PHASEA_CHUNK != 0 && (C::POS || NC > 0);
+    // (a single player of the double integrator has neither position blocks nor Jacobian coefficients: no phase A at all)
+    constexpr bool PCH = C::POS || NC > 0;
     static_assert(!PCH || (FT + 1) * P <= NT, "one phase-A item per lane and chunk");
-    if constexpr (!PCH) assemble_phase_a<C, MODE, false, DUAL>(pr, G, L, zs, AXPY ? dz : nullptr, alpha, N, lane, dt, -1, acc, dual);
     LSP(20)
     const bool pairs_on = P > 1 && (pr.has_colcost || pr.has_colavoid);
     auto& Ch = L.ch;
@@ -639,11 +576,11 @@ __device__ void assemble_fused(CPR pr0, const Game& G0, AsmLds<C>& L, double alp
     for (int k0 = 0; k0 < N - 1; k0 += FT) {
         const int nst = (N - 1 - k0) < FT ? (N - 1 - k0) : FT;            // steps of this chunk
         const int nblk = (k0 + nst < N - 1) ? nst + 1 : nst;             // blocks staged: the chunk's and the next one (A' lambda_{k+1})
-        // (PCH) multipliers / penalties of this lane's phase-A item, requested ahead of the chunk's blocks
+        // multipliers / penalties of this lane's phase-A item, requested ahead of the chunk's blocks
         constexpr int NPR = P > 1 ? P - 1 : 1;
         const int aks = lane / P, ai = lane % P;                          // phase-A item of this lane: (step k0 + aks, player ai)
         double plm[NPR], pmu[NPR];
-        if constexpr (PCH && C::POS) {
+        if constexpr (C::POS) {
 #pragma unroll
             for (int jj = 0; jj < NPR; jj++) { plm[jj] = 0.0; pmu[jj] = 0.0; }
             if (pairs_on && pr.has_colavoid && aks < nst) {
@@ -662,65 +599,16 @@ __device__ void assemble_fused(CPR pr0, const Game& G0, AsmLds<C>& L, double alp
             Ch.xprev[lane] = v;
         }
         {
-            const int base = n + k0 * b, cnt = nblk * b, own = nst * b;
-#if ALG_R6_STAGE
-            // Round 6: EVERY global load of the chunk -- the blocks of z and dz, the pair-gradient tables, the Jacobian coefficients -- is issued
-            // before the first one is waited for.  (Round 4's loop fetched four elements per lane and trip and the tables one per trip: a chunk of
-            // C2 exposed seven global round trips in a row, a pass twenty-one, with four games per SIMD streaming at the same time.)
-            // (batches of SB elements per lane: all of them at once -- 12 x 2 doubles per lane at C2 -- overflows the 128-register budget)
+            const int base = n + k0 * b, cnt = nblk * b;
+            // Every global load of the chunk's blocks of z and dz is issued before the first one is waited for, in batches of SB elements per lane
+            // (all of them at once -- 12 x 2 doubles per lane at C2 -- overflows the 128-register budget; the record pass loads z alone).
             constexpr int SU = ((FT + 1) * b + NT - 1) / NT;              // elements per lane of the largest chunk (C2: 12)
-            // (the record pass loads z alone -- half the registers per element: ALG_R6_STAGE_BATCH_REC elements per batch)
-            constexpr int SB4 = AXPY ? ALG_R6_STAGE_BATCH : (ALG_R6_STAGE_BATCH_REC < SU ? ALG_R6_STAGE_BATCH_REC : SU);
-            constexpr int SB = C::WPE == 4 ? SB4 : (SU < ALG_R6_STAGE_BATCH_W2 ? SU : ALG_R6_STAGE_BATCH_W2);
-            constexpr int TU = C::POS ? (FT * TAB + NT - 1) / NT : 1, CU = NC > 0 ? ((FT + 1) * NC + NT - 1) / NT : 1;
-            double gt[TU], cf[CU];
-            const int tcnt = nst * TAB, ccnt = nblk * NC;
-            if constexpr (C::POS && !PCH) {
-#pragma unroll
-                for (int t = 0; t < TU; t++) { const int e = lane + t * NT; gt[t] = gld(recg + R::gvt(N, k0), e < tcnt ? e : 0); }            // contiguous behind the records
-            }
-            if constexpr (NC > 0 && !PCH) {                                // Jacobian coefficients of the staged steps (phase A left them in the records)
-#pragma unroll
-                for (int t = 0; t < CU; t++) { const int e = lane + t * NT, ec = e < ccnt ? e : 0; cf[t] = gld(recg, (k0 + ec / NC) * R::LEN + R::COEF + ec % NC); }
-            }
+            constexpr int SB4 = AXPY ? FT_STAGE_BATCH : (FT_STAGE_BATCH_REC < SU ? FT_STAGE_BATCH_REC : SU);
+            constexpr int SB = C::WPE == 4 ? SB4 : (SU < FT_STAGE_BATCH_W2 ? SU : FT_STAGE_BATCH_W2);
             // Lanes past the end of the chunk repeat its last element (clamped index) instead of being masked off: they load, form and store the
             // very value the owning lane does -- same address, same bits -- so no per-element exec mask has to be kept in scalar registers.  The
             // trial values of the chunk's extra block (A_{k+1}' lambda_{k+1}) go out here as well as with the next chunk: the same bits twice.
-            // Round 6 (lane roles, ALG_R6_LANEROLE >= 2): a lane stages the same entry of every block (NT / b blocks per trip, the trips unrolled): the
-            // element of trip T is (T BS b + lane) -- a chunk-invariant lane offset plus an immediate in every address, no clamps, no (block, entry)
-            // divided out of a flat index for the [x | u] copy; b of NT lanes work (C2: 54 of 64, 14 trips for 12).
-            // Measured and NOT taken (profiles/r06_ab_lr2_c2.txt): bit-identical, but C2 14.08 against 14.55 M/s with the flat staging -- fewer loads in
-            // flight per batch (four blocks where the flat loop holds six elements of z and dz; five already spill) and ten idle lanes cost more than
-            // the index arithmetic saved.  The default build keeps ALG_R6_LANEROLE 1 (rows only).
-            constexpr bool SLR = ALG_R6_LANEROLE >= 2 && C::MODEL == ALG_MODEL_DOUBLE_INTEGRATOR && !ALG_LSM_DI1W && b <= NT;
-            if constexpr (SLR) {
-                constexpr int BS = NT / b, BT = (FT + 1 + BS - 1) / BS, SBL = BT < ALG_R6_STAGE_BATCH_LR ? BT : ALG_R6_STAGE_BATCH_LR;
-                int sl = lane; asm volatile("" : "+v"(sl)); __builtin_assume(sl >= 0 && sl < NT);
-                const int lb = sl / b, o = sl % b;
-                if (lb < BS) {
-                    const bool isxu = o < NXU;
-                    double* const lxu = Ch.zxu + lb * NXU + o;
-#pragma unroll
-                    for (int t0 = 0; t0 < BT; t0 += SBL) {
-                        double a[SBL], d[SBL];
-#pragma unroll
-                        for (int t = 0; t < SBL; t++) {
-                            const int T = t0 + t, j = BS == 1 ? T : T * BS + lb;
-                            if (T < BT && j < nblk) { a[t] = gld(zs + base + T * BS * b, sl); d[t] = AXPY ? gld(dz + base + T * BS * b, sl) : 0.0; }
-                        }
-#pragma unroll
-                        for (int t = 0; t < SBL; t++) {
-                            const int T = t0 + t, j = BS == 1 ? T : T * BS + lb;
-                            if (T < BT && j < nblk) {
-                                const double v = AXPY ? __builtin_fma(alpha, d[t], a[t]) : a[t];
-                                Ch.zt[T * BS * b + sl] = v;
-                                if (AXPY) gst(zo + base + T * BS * b, sl, v);
-                                if (isxu && j < nst) lxu[T * BS * NXU] = a[t];
-                            }
-                        }
-                    }
-                }
-            } else
+            // (a lane-role staging -- the same entry of every block per lane -- was measured and not taken: profiles/r06_ab_lr2_c2.txt)
 #pragma unroll
             for (int t0 = 0; t0 < SU; t0 += SB) {
                 if (t0 * NT >= cnt) break;                                  // (wave-uniform: the last chunk of a horizon is shorter)
@@ -742,40 +630,6 @@ __device__ void assemble_fused(CPR pr0, const Game& G0, AsmLds<C>& L, double alp
                     *xu = a[t];
                 }
             }
-            if constexpr (C::POS && !PCH) {
-#pragma unroll
-                for (int t = 0; t < TU; t++) { const int e = lane + t * NT; if (e < tcnt) Ch.gvt[e] = gt[t]; }
-            }
-            if constexpr (NC > 0 && !PCH) {
-#pragma unroll
-                for (int t = 0; t < CU; t++) { const int e = lane + t * NT; if (e < ccnt) Ch.coef[e] = cf[t]; }
-            }
-#else
-            for (int e0 = lane; e0 < cnt; e0 += 4 * NT) {
-                double a[4], d[4];
-#pragma unroll
-                for (int t = 0; t < 4; t++) { const int e = e0 + t * NT, ec = e < cnt ? e : e0; a[t] = gld(zs + base, ec); d[t] = AXPY ? gld(dz + base, ec) : 0.0; }
-#pragma unroll
-                for (int t = 0; t < 4; t++) {
-                    const int e = e0 + t * NT;
-                    if (e < cnt) {
-                        const double v = AXPY ? __builtin_fma(alpha, d[t], a[t]) : a[t];
-                        Ch.zt[e] = v;
-                        if (AXPY && e < own) gst(zo + base, e, v);
-                        const int j = e / b, o = e % b;
-                        if (o < NXU && j < nst) Ch.zxu[j * NXU + o] = a[t];
-                    }
-                }
-            }
-            if constexpr (C::POS) {
-                const int tcnt = nst * TAB;
-                for (int e = lane; e < tcnt; e += NT) Ch.gvt[e] = gld(recg + R::gvt(N, k0), e);            // contiguous behind the records
-            }
-            if constexpr (NC > 0) {                                        // Jacobian coefficients of the staged steps (phase A left them in the records)
-                const int ccnt = nblk * NC;
-                for (int e = lane; e < ccnt; e += NT) Ch.coef[e] = recg[(size_t)(k0 + e / NC) * R::LEN + R::COEF + e % NC];
-            }
-#endif
         }
         fsync();
         if constexpr (PCH) {
@@ -818,7 +672,7 @@ __device__ void assemble_fused(CPR pr0, const Game& G0, AsmLds<C>& L, double alp
         // and selects on it.  opt_x rows: NT / (P n) steps per trip (C2: one, 36 of 64 lanes, 13 trips for 8 -- but a fifth of the instructions
         // each); opt_u rows NT / m steps per trip, dyn rows NT / n (C2: ten and five: the same number of trips as before).  Every row is the
         // same expression as before; a lane sums other rows than it did, so the l1 norms move in the last bits.  The one-wavefront unicycle kernels keep the flat dealing
-        // (lane_roles_v: with ALG_R6_LANEROLE_UNI the line search's group pass deals its rows by lane roles too and stays bit-identical -- measured, not taken).
+        // (lane roles there too were measured and not taken: profiles/r06_ab_lru_*.txt).
         constexpr int RPS = P * n;
         constexpr bool LR = lane_roles_v<C>;
         // (the roles are worked out per chunk from an opaque copy of the lane id: as invariants of the whole pass they would be hoisted in front
@@ -859,20 +713,14 @@ __device__ void assemble_fused(CPR pr0, const Game& G0, AsmLds<C>& L, double alp
                 for (int t = 0; t < XT; t++) { const int ks = XS == 1 ? t : t * XS + ls; if (ks < nst) xrow(ks, ei, i, a, tq, tx); }
             }
         } else {
-#if ALG_R6_ROWIDX
         // (row e = lane + NT t of the chunk, as (step, entry) = divmod(e, P n), carried from trip to trip instead of divided out again)
         constexpr int RDQ = NT / RPS, RDR = NT % RPS;
         int rks = lane / RPS, rei = lane % RPS;
-#endif
         for (int e = lane; e < nst * P * n; e += NT) {
-#if ALG_R6_ROWIDX
             __builtin_assume(rei >= 0 && rei < RPS);
             const int ks = rks, ei = rei, i = ei / n, a = ei % n;
             rks += RDQ; rei += RDR;
             if (rei >= RPS) { rei -= RPS; rks += 1; }
-#else
-            const int ks = e / (P * n), ei = e % (P * n), i = ei / n, a = ei % n;
-#endif
             double tq, tx; xconst(i, a, tq, tx);
             xrow(ks, ei, i, a, tq, tx);
         }
@@ -992,18 +840,14 @@ __device__ void assemble_fused(CPR pr0, const Game& G0, AsmLds<C>& L, double alp
 // Phase A's per-step-size output -- Jacobian coefficients and pair-gradient tables -- goes to the gain scratch (dead outside the direction).
 //   base constraint set of the double integrator / unicycle only (collision cost, collision avoidance, control bounds)
 // ================================================================================================
-#ifndef ALG_LSM_DI1W
-#define ALG_LSM_DI1W 0        // 1: the group pass on the one-wavefront double-integrator kernels as well.  Measured in round 6 and not
-                              // taken: bit-identical, 126 VGPRs, but neutral to -1 % on perturbed C2 / C4 batches with and without the hand-off -- their
-                              // stragglers take many iterations, not deep searches (profiles/r06_ab_lsm_di1w_*.txt)
-#endif
+// (the group pass on the one-wavefront double-integrator kernels as well was measured and not taken: profiles/r06_ab_lsm_di1w_*.txt)
 template <class C> struct LsMulti {
     // team kernels (whose ordinary trial pass is assemble_pass: all rows of a kind in one flat loop) and the one-wavefront unicycle kernels (fused
     // trial pass: the rows chunk by chunk -- the group pass deals and sums its rows in the same order, CHUNK steps at a time).  Norms bit-identical
     // in both cases.  (On the one-wavefront kernels they first came out an ulp apart in one of ten candidates: BT_vec's `a b + c d` had been
     // contracted one way in the fused pass and the other way here; BT_vec now states its fmas.)
     static constexpr bool TEAMS = C::NW > 1 && !AsmLds<C>::FUSED && (C::MODEL == ALG_MODEL_DOUBLE_INTEGRATOR || C::MODEL == ALG_MODEL_UNICYCLE);
-    static constexpr bool ONEW = C::NW == 1 && AsmLds<C>::FUSED && (C::MODEL == ALG_MODEL_UNICYCLE || ALG_LSM_DI1W);
+    static constexpr bool ONEW = C::NW == 1 && AsmLds<C>::FUSED && C::MODEL == ALG_MODEL_UNICYCLE;
     static constexpr bool ON = (TEAMS || ONEW) && !C::EXT && !C::DENSE && C::POS;
     static constexpr int CHUNK = ONEW ? AsmLds<C>::FT : (1 << 20);
     static constexpr int NA = LS_NA;                          // step sizes per pass
@@ -1113,8 +957,6 @@ __device__ void trial_norms_multi(CPR pr0, const Game& G0, const double* lz, dou
     auto add = [&](int q, double r, double dprox) { const double rr = prox ? r + reg * dprox : r; l1[q] += fabs(rr); };
     for (int k0 = 0; k0 < N - 1; k0 += LsMulti<C>::CHUNK) {            // (one chunk = the whole horizon for the team kernels)
     const int nst = (N - 1 - k0) < LsMulti<C>::CHUNK ? (N - 1 - k0) : LsMulti<C>::CHUNK;
-    // (one-wavefront kernels whose fused pass deals its rows by lane roles: the same dealing here -- per lane the same rows in the same order)
-    constexpr bool LRG = LsMulti<C>::ONEW && lane_roles_v<C>;
     // ---- rows opt_i,x_{k+1}[a]
     auto gx = [&](int ks, int ei) {
         const int k = k0 + ks, i = ei / n, a = ei % n;
@@ -1140,11 +982,7 @@ __device__ void trial_norms_multi(CPR pr0, const Game& G0, const double* lz, dou
             add(q, r, xa - xr);
         }
     };
-    if constexpr (LRG) {
-        constexpr int RPS = P * n, XS = NT / RPS;
-        const int ls = lane / RPS, ei = lane % RPS;
-        if (ls < XS) for (int ks = ls; ks < nst; ks += XS) gx(ks, ei);
-    } else for (int e = lane; e < nst * P * n; e += NT) gx(e / (P * n), e % (P * n));
+    for (int e = lane; e < nst * P * n; e += NT) gx(e / (P * n), e % (P * n));
     // ---- rows opt_i,u_{i,k}[c]
     auto gu = [&](int ks, int c) {
         const int k = k0 + ks, i = c % P;
@@ -1175,11 +1013,7 @@ __device__ void trial_norms_multi(CPR pr0, const Game& G0, const double* lz, dou
             add(q, r, u - ur);
         }
     };
-    if constexpr (LRG) {
-        constexpr int US = NT / m;
-        const int ls = lane / m, c = lane % m;
-        if (ls < US) for (int ks = ls; ks < nst; ks += US) gu(ks, c);
-    } else for (int e = lane; e < nst * m; e += NT) gu(e / m, e % m);
+    for (int e = lane; e < nst * m; e += NT) gu(e / m, e % m);
     // ---- rows dyn_k[a]
     auto gd = [&](int ks, int a) {
         const int k = k0 + ks;
@@ -1204,11 +1038,7 @@ __device__ void trial_norms_multi(CPR pr0, const Game& G0, const double* lz, dou
             add(q, xn - tv(q, zo + a), 0.0);
         }
     };
-    if constexpr (LRG) {
-        constexpr int DS = NT / n;
-        const int ls = lane / n, a = lane % n;
-        if (ls < DS) for (int ks = ls; ks < nst; ks += DS) gd(ks, a);
-    } else for (int e = lane; e < nst * n; e += NT) gd(e / n, e % n);
+    for (int e = lane; e < nst * n; e += NT) gd(e / n, e % n);
     }
     // ---- the team's sums, wavefront by wavefront like team_combine
     __shared__ double redm[C::NW][NA];

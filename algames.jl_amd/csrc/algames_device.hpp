@@ -31,7 +31,8 @@
 // ALG_SWEEP_DEPTH / ALG_SWEEP_DEPTH_W2 / ALG_FWDW_DEPTH (prefetch rings of the sweeps) and ALG_RDG_W2 / ALG_RDG_W4 (coefficient groups of the
 // row-broadcast chains), and the instrumentation builds ALG_PHASE_PROF (per-phase cycle sums), ALG_ISA_MARK (phase markers in the ISA),
 // ALG_DIR_STOP (direction cut after a sweep, for per-sweep counters) and ALG_NO_REFINE (refinement gate compiled out).  The A/B switches
-// of rounds 3 - 4 whose outcome is recorded in DESIGN.md section 8 were resolved to their shipped side in round 5.
+// of rounds 3 - 6 whose outcome is recorded in DESIGN.md (sections 4, 8, 9) and profiles/README.md were resolved to their shipped side; a
+// variant that was measured and not taken can be rebuilt from the commit before its removal.
 
 namespace alg {
 
@@ -39,6 +40,10 @@ namespace alg {
 constexpr int FT_DI3 = 13;     // time steps per chunk of the fused trial pass, 3-player double integrator (the chunk buffers fill the LDS that sixteen games per CU leave)
 constexpr int FT_UNI3 = 15;    // 3-player unicycle: twelve games per CU (3 x 152 VGPRs per SIMD) leave 13.3 KB each; N = 30 is two chunks
 constexpr int FT_UNI4 = 13;    // 4-player unicycle: the chunk buffers stay under the direction's 18.2 KB
+// Staging of the fused trial pass (round 6): elements per lane whose global loads are in flight before the first wait
+constexpr int FT_STAGE_BATCH = 6;      // z and dz, 128-register kernels (all twelve of C2 at once overflow the budget; five already spill with lane-role staging: profiles/r06_ab_lr2_c2.txt)
+constexpr int FT_STAGE_BATCH_REC = 6;  // z alone (record pass), 128-register kernels (all twelve in one batch: neutral, profiles/r06_ab_rec12_c2.txt)
+constexpr int FT_STAGE_BATCH_W2 = 10;  // 256-register kernels (the 4-player unicycle's chunk is 20 elements per lane: 40 doubles in flight at once spilled its loop kernel)
 constexpr int LS_CAP = 3200;   // doubles of LDS for [z | dz] of a line search (LsLds)
 constexpr int LS_SCAP = 3520;  // doubles of LDS for the group pass's Jacobian coefficients and pair-gradient tables (teams of four)
 constexpr int LS_NA = 4;       // step sizes per group pass of the team kernels' line search (LsMulti, algames_assemble.hpp)
@@ -205,6 +210,10 @@ struct Cfg {
 #ifndef ALG_SWEEP_DEPTH_W2
 #define ALG_SWEEP_DEPTH_W2 4       // 256-register kernels (2 until late in round 6; 4: bit-identical, C3 +1.6 %, C5 loop +1.5 %, C5 / C3 at 4096 games +2.8 / +3.9 %: profiles/r06_ab_sdw4_*.txt)
 #endif
+    // forward sweep of the double integrator, w_k chain: steps in flight (three doubles per slot, direction_forward_costate)
+#ifndef ALG_FWDW_DEPTH
+#define ALG_FWDW_DEPTH 8
+#endif
     static constexpr int SWEEP_DEPTH = WPE == 4 ? ALG_SWEEP_DEPTH : (ALG_SWEEP_DEPTH < ALG_SWEEP_DEPTH_W2 ? ALG_SWEEP_DEPTH : ALG_SWEEP_DEPTH_W2);
     // rows per lane and pass of the assemble row loops (memory-level parallelism against the L2 / store-ack latency)
 #ifndef ALG_ASM_UNROLL_W2
@@ -238,24 +247,12 @@ template <class C> __device__ __forceinline__ const double* zstate(const double*
 // Every kernel runs one game per workgroup (one wavefront, or a team of Cfg::NW), so the game's thread index is the workgroup's
 // and its barrier is the workgroup barrier.
 __device__ __forceinline__ int game_tid() { return (int)threadIdx.x; }
-// (measured in round 6: 63 of the C2 kernel's 194 full 32-bit multiplies become 24-bit ones, the rate does not move -- profiles/r06_ab_lane_range_c2.txt --
-// and the 4-player DoubleIntegrator d = 1 kernel starts to spill: off)
-#ifndef ALG_R6_LANE_RANGE
-#define ALG_R6_LANE_RANGE 0
-#endif
 __device__ __forceinline__ void game_sync() { __syncthreads(); }
 // ---- wave reductions ---------------------------------------------------------------------------
 // Opaque copy of the lane id: keeps per-lane role / address computations of a phase from being hoisted out of the
 // solver's outer loops (where every phase's invariants would be live at once).
-// (ALG_R6_LANE_RANGE: the copy keeps the id's value range -- a workgroup has at most 256 threads -- so that products of lane-derived indices can take
-// the 24-bit multiply)
-__device__ __forceinline__ int phase_lane() {
-    int l = game_tid(); asm volatile("" : "+v"(l));
-#if ALG_R6_LANE_RANGE
-    __builtin_assume((unsigned)l < 256u);
-#endif
-    return l;
-}
+// (telling the compiler the copy's value range, for 24-bit multiplies of lane-derived indices, was measured and not taken: profiles/r06_ab_lane_range_c2.txt)
+__device__ __forceinline__ int phase_lane() { int l = game_tid(); asm volatile("" : "+v"(l)); return l; }
 // Opaque copies of wave-uniform loop invariants (problem sizes, dt, base pointers), taken at the start of a phase: whatever is
 // derived from them (row counts, address vectors, dt^2 / 2, (double)S ...) is recomputed inside the phase with a handful of
 // scalar instructions instead of being hoisted in front of the solver's outer loops and kept alive -- or spilled -- there.

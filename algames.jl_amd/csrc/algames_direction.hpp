@@ -294,7 +294,7 @@ __device__ __forceinline__ void rowdot_dpp_g(double& acc, double v, PF&& p) {
     if constexpr (G <= 0) rowdot_dpp_f<NC>(acc, v, p);
     else { double cur[G]; rowdot_group_load<0, G, NC>(cur, p); rowdot_pipe<NC, G, 0>(acc, v, p, cur); }
 }
-// Two interleaved half-chains (round 6, ALG_R6_ROWDOT_SPLIT): terms 0 .. H-1 accumulate into acc, terms H .. NC-1 into a second accumulator, the two
+// Two interleaved half-chains (round 6): terms 0 .. H-1 accumulate into acc, terms H .. NC-1 into a second accumulator, the two
 // are added at the end -- the dependent chain is H + 1 instructions long instead of NC.  A lone wavefront waits out every link of these chains (the
 // forward sweep's du = -(Y dx + y0), the backward sweep's y_i = P_i rd + s_i: 12 links each at C2).  Another association of the same sum: results
 // move at rounding level against the single chain.  Coefficients are requested in groups of G (two terms of each half per group of four).
@@ -328,73 +328,14 @@ __device__ __forceinline__ void rowdot_dpp_split(double& acc, double v, PF&& p) 
     rowdot_split_pipe<NC, H, 0, G2>(acc, b2, v, p, ca, cb);
     acc += b2;
 }
-// The same with NCH interleaved sub-chains (terms [j H, (j + 1) H) on accumulator j, H = ceil(NC / NCH); accumulators added pairwise at the end):
-// dependent length H + ceil(log2 NCH).  NCH = 2 is rowdot_dpp_split's association exactly.
-template <int NC, int NCH, int H, int I, int G2, class PF, int... Ts>
-__device__ __forceinline__ void rowdot_chains_load(double (&c)[NCH][G2], PF&& p, std::integer_sequence<int, Ts...>) {
-    (([&] { constexpr int t = Ts / NCH, j = Ts % NCH, term = j * H + I + t; c[j][t] = (I + t < H && term < NC) ? p(term < NC ? term : 0) : 0.0; }()), ...);
-}
-template <int NC, int NCH, int H, int I, int G2, int... Ts>
-__device__ __forceinline__ void rowdot_chains_fmac(double (&acc)[NCH], double v, const double (&c)[NCH][G2], std::integer_sequence<int, Ts...>) {
-    (([&] { constexpr int t = Ts / NCH, j = Ts % NCH, term = j * H + I + t;
-            if constexpr (I + t < H && term < NC) fmac_rowbcast<term, (I + t == 0 && j == 0)>(acc[j], v, c[j][t]); }()), ...);
-}
-template <int NC, int NCH, int H, int I, int G2, class PF>
-__device__ __forceinline__ void rowdot_chains_pipe(double (&acc)[NCH], double v, PF&& p, const double (&cur)[NCH][G2]) {
-    using Seq = std::make_integer_sequence<int, NCH * G2>;
-    if constexpr (I + G2 < H) {
-        double nxt[NCH][G2];
-        rowdot_chains_load<NC, NCH, H, I + G2, G2>(nxt, p, Seq{});
-        rowdot_chains_fmac<NC, NCH, H, I, G2>(acc, v, cur, Seq{});
-        rowdot_chains_pipe<NC, NCH, H, I + G2, G2>(acc, v, p, nxt);
-    } else rowdot_chains_fmac<NC, NCH, H, I, G2>(acc, v, cur, Seq{});
-}
-template <int NC, int NCH, int G, class PF>
-__device__ __forceinline__ void rowdot_dpp_chains(double& acc0, double v, PF&& p) {
-    static_assert(NCH >= 2 && NCH <= 4, "two to four sub-chains");
-    constexpr int H = (NC + NCH - 1) / NCH, G2 = (G >= NCH ? G / NCH : 1);
-    double acc[NCH], cur[NCH][G2];
-    acc[0] = acc0;
-#pragma unroll
-    for (int j = 1; j < NCH; j++) acc[j] = 0.0;
-    rowdot_chains_load<NC, NCH, H, 0, G2>(cur, p, std::make_integer_sequence<int, NCH * G2>{});
-    rowdot_chains_pipe<NC, NCH, H, 0, G2>(acc, v, p, cur);
-    if constexpr (NCH == 2) acc0 = acc[0] + acc[1];
-    else if constexpr (NCH == 3) acc0 = (acc[0] + acc[1]) + acc[2];
-    else acc0 = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-}
-// (measured, profiles/r06_ab_rowdot_chains_c2.txt: three sub-chains neutral, four 2 % slower than two -- the extra accumulators' adds and the
-// wider coefficient groups cost what the shorter chain saves; the w_k chain in two halves: neutral.  Two it is.)
-#ifndef ALG_R6_ROWDOT_CHAINS
-#define ALG_R6_ROWDOT_CHAINS 2
-#endif
-#ifndef ALG_R6_SADDR
-#define ALG_R6_SADDR 1            // per-step base addresses of the sweeps' global accesses forced into scalar registers (uniform_u64): 1 gain stores and
-                                  // forward-sweep prefetches (C2 +1.5 ... 2.6 %, profiles/r06_ab_saddr_*.txt); 2 also the backward sweep's record prefetch as
-                                  // unconditional clamped loads -- measured 0.7 ... 2 % SLOWER at C2 / C4 (r06_ab_saddr_prefetch_*.txt), not taken
-#endif
-#ifndef ALG_R6_CURC
-#define ALG_R6_CURC 1             // forward sweep: LDS double-buffer index of a step as a compile-time constant of the unrolled loop
-#endif
-#ifndef ALG_R6_PL1
-#define ALG_R6_PL1 1              // forward sweep: |du| + |dx| summed and checked without per-step lane masks
-#endif
-#ifndef ALG_R6_FWD_LAND
-#define ALG_R6_FWD_LAND 0         // where a forward-sweep step lands the next step's prefetched slice in LDS: 0 at its tail, 1 behind its first LDS reads, 2 behind the du chain
-#endif                            // (measured at C2, profiles/r06_ab_fwd_land_c2.txt: 1 -0.6 %, 2 neutral)
-#ifndef ALG_R6_WCHAIN_SPLIT
-#define ALG_R6_WCHAIN_SPLIT 0      // the forward sweep's w_k = rx + Q^ dx chain (double integrator, FWDW) as two half-chains
-#endif
+// (three / four sub-chains and the forward sweep's w_k chain in two halves were measured and not taken: profiles/r06_ab_rowdot_chains_c2.txt)
 // Measured in round 6, same box, alternating (profiles/r06_ab_rowdot_split_*.txt, r06_ab_rdone_*.txt): C2 +0.8 ... 1.5 % on one box, +0.6 ... 2.7 % on two
 // others; C3 and C2 at 512 games neutral; the C5 loop (64 seeds x 200 steps, one launch = its slowest seed) 240 -> 202 K/s: no kernel effect -- at 100
 // steps both forms take 186 ms -- but another rounding of the closed-loop trajectories, on which another seed meets a long line-search episode.
 // So: the double-integrator kernels (every shape of them, so that they stay bit-identical with each other) form these two sums as half-chains,
 // the unicycle / bicycle kernels keep the single chain -- nothing to gain there, and their calibrated accuracy tests (tests/test_gpu_refinement.py)
 // and the BASELINE C5 trajectories stay what they were.
-#ifndef ALG_R6_ROWDOT_SPLIT
-#define ALG_R6_ROWDOT_SPLIT 1
-#endif
-template <class C> inline constexpr bool rowdot_split_v = ALG_R6_ROWDOT_SPLIT != 0 && C::MODEL == ALG_MODEL_DOUBLE_INTEGRATOR;
+template <class C> inline constexpr bool rowdot_split_v = C::MODEL == ALG_MODEL_DOUBLE_INTEGRATOR;
 #ifndef ALG_RDG_W2
 #define ALG_RDG_W2 16         // coefficient group of the row-broadcast chains, 256-register kernels (0: fetch where used)
 #endif
@@ -1581,15 +1522,10 @@ __device__ __forceinline__ int direction_forward_costate(CPR pr, const Game& G0,
     // LDS, (2) issue this step's result stores, (3) request the data of step k+2 -- the single wait of a step meets loads and
     // stores that have been in flight for a whole step.
     auto fwd_load = [&](int kk, double (&rf)[FPL], double (&rk)[KPL]) {
-#if ALG_R6_SADDR
         const int kc = __builtin_amdgcn_readfirstlane(kk < N - 1 ? kk : N - 2);
         // (the step's two base addresses as scalar pairs, see the gain stores of the backward sweep)
         const double* const Rb = as_global(reinterpret_cast<const double*>(uniform_u64(reinterpret_cast<unsigned long long>(G.rec(pr) + (size_t)kc * R::LEN))));
         const double* const Kb = as_global(reinterpret_cast<const double*>(uniform_u64(reinterpret_cast<unsigned long long>(G.kgain(pr) + (size_t)kc * NK))));
-#else
-        const int kc = kk < N - 1 ? kk : N - 2;
-        const double* const Rb = G.rec(pr) + (size_t)kc * R::LEN; const double* const Kb = G.kgain(pr) + (size_t)kc * NK;
-#endif
 #pragma unroll
         for (int q = 0; q < FPL; q++) rf[q] = gld(Rb, fso[q]);
 #pragma unroll
@@ -1619,41 +1555,30 @@ __device__ __forceinline__ int direction_forward_costate(CPR pr, const Game& G0,
       for (int u = 0; u < SD; u++) {
         const int k = k0 + u;
         if (k >= N - 1) break;
-#if ALG_R6_CURC
         // (the LDS double buffer's index as a compile-time constant of the unrolled step -- SD is even, the sweep starts at slot 0 -- so that every LDS
         // address of the step is a loop-invariant lane offset plus an immediate: with a run-time index each of the step's ~13 addresses was re-formed)
         static_assert(SD % 2 == 0 || SD == 1, "sweep depth");
         const int cur = (SD % 2 == 0) ? (u & 1) : curv;
-#else
-        const int cur = curv;
-#endif
         const double* Rc = L.rec[cur]; const double* Kl = L.fw.kg[cur];
         const int fl = FWDW ? (lane & 15) : lane;     // FWDW: every 16-lane row runs the recursion (same LDS addresses, same instructions)
         const int cl = fl < m ? fl : 0;
         double acc = Kl[n * m + cl];
         auto land_next = [&]() {
-            // (1) data of step k+1 (requested SD steps ago) -> LDS (clamped duplicates at the last steps are never read)
+            // (1) data of step k+1 (requested SD steps ago) -> LDS (clamped duplicates at the last steps are never read); called at the step's tail
+            // (behind the first LDS reads or behind the du chain: measured and not taken, profiles/r06_ab_fwd_land_c2.txt)
 #pragma unroll
             for (int q = 0; q < FPL; q++) L.rec[cur ^ 1][fso[q]] = pref[(u + 1) % SD][q];
 #pragma unroll
             for (int q = 0; q < KPL; q++) { const int e = lane + q * WAVE; L.fw.kg[cur ^ 1][e < NK ? e : NK - 1] = prek[(u + 1) % SD][q]; }
         };
-        if constexpr (ALG_R6_FWD_LAND == 1) land_next();
-        if constexpr (rowdot_split_v<C> && ALG_R6_ROWDOT_CHAINS > 2) rowdot_dpp_chains<n, ALG_R6_ROWDOT_CHAINS, (rowdot_group_v<C> < n ? rowdot_group_v<C> : n)>(acc, dxr, [&](int q) { return Kl[q * m + cl]; });
-        else if constexpr (rowdot_split_v<C>) rowdot_dpp_split<n, (rowdot_group_v<C> < n ? rowdot_group_v<C> : n)>(acc, dxr, [&](int q) { return Kl[q * m + cl]; });
+        if constexpr (rowdot_split_v<C>) rowdot_dpp_split<n, (rowdot_group_v<C> < n ? rowdot_group_v<C> : n)>(acc, dxr, [&](int q) { return Kl[q * m + cl]; });
         else rowdot_dpp_g<n, (rowdot_group_v<C> < n ? rowdot_group_v<C> : n)>(acc, dxr, [&](int q) { return Kl[q * m + cl]; });                  // dx_k sits in lanes 0..n-1 of the row, the control rows in its lanes 0..m-1 (same FMA order as the v_readlane form)
-        if constexpr (ALG_R6_FWD_LAND == 2) land_next();
         const double duv = fl < m ? (SPLITF ? -acc : acc) : 0.0;     // (split recursion: the gains in HBM are -[K | kappa])
         const double rdv = Rc[R::RD + (fl < n ? fl : 0)];
         double dxn = fwd_next<C>(Rc + R::COEF, dt, dxr, duv, fl) + rdv;
         dxn = fl < n ? dxn : 0.0;
-#if ALG_R6_PL1
         pl1 += fabs(duv); pl1 += fabs(dxn);
         badm |= __builtin_amdgcn_ballot_w64(!isfinite(duv)) | __builtin_amdgcn_ballot_w64(!isfinite(dxn));
-#else
-        if (lane < m) { pl1 += fabs(duv); badm |= __builtin_amdgcn_ballot_w64(!isfinite(duv)); }
-        if (lane < n) { pl1 += fabs(dxn); badm |= __builtin_amdgcn_ballot_w64(!isfinite(dxn)); }
-#endif
         dxr = dxn;
         if constexpr (FWDW) {
             // w_k = rx_{i,k+1} + Q^_{i,k+1} dx_{k+1} for (player, row) = (ri_, rr_): the head of the costate sweep's FMA sequence
@@ -1666,13 +1591,12 @@ __device__ __forceinline__ int direction_forward_costate(CPR pr, const Game& G0,
 #pragma unroll
                 for (int c = 0; c < NPOS; c++) hv[c] = (double)hsg[c] * Rc[hso[c]];
                 double t = wk;
-                if constexpr (ALG_R6_WCHAIN_SPLIT != 0 && rowdot_split_v<C>) rowdot_dpp_split<NPOS, NPOS>(t, dxn, [&](int c) { return hv[c]; });
-                else rowdot_dpp<NPOS>(t, dxn, hv);
+                rowdot_dpp<NPOS>(t, dxn, hv);
                 wk = rr_ < C::PD * P ? t : wk;
             }
             if (rok) gst(dz + n + hl<C>(k, 0), re_, wk);
         }
-        if constexpr (ALG_R6_FWD_LAND == 0) land_next();
+        land_next();
         asm volatile("" ::: "memory");
         // (2) results out
         if (lane < m) gst(dz + n + hu<C>(k, 0), uoff<C>(lane), duv);
@@ -1702,9 +1626,6 @@ __device__ __forceinline__ int direction_forward_costate(CPR pr, const Game& G0,
         // dlambda_k = w_k + A_{k+1}' dlambda_{k+1}: w_k comes back from dlambda's own slot (this lane wrote it in the forward sweep), the
         // coefficients of A_{k+1} (state-dependent models) from step k + 1's record; SD steps in flight, no LDS, no fence
         constexpr int NCF = C::NC > 0 ? (C::MODEL == ALG_MODEL_BICYCLE ? 3 : 2) : 0;
-#ifndef ALG_FWDW_DEPTH
-#define ALG_FWDW_DEPTH 8
-#endif
         constexpr int CD = ALG_FWDW_DEPTH;           // steps in flight: three doubles per slot, and nothing but these loads feeds the recursion
         double wkr[CD], cfr[CD][NCF > 0 ? NCF : 1];
         auto cw_load = [&](int kk, double& wv, double (&cf)[NCF > 0 ? NCF : 1]) {
@@ -1768,11 +1689,7 @@ __device__ __forceinline__ int direction_forward_costate(CPR pr, const Game& G0,
       for (int u = 0; u < SD; u++) {
         const int k = k0 - u;
         if (k < 0) break;
-#if ALG_R6_CURC
         const int cur = (SD % 2 == 0) ? (u & 1) : curc;      // (compile-time slot index, like the forward sweep)
-#else
-        const int cur = curc;
-#endif
         const double* Rc = L.rec[cur];
         const double w = (k + 1 < N - 1) ? dt : 1.0;
         if constexpr (DIROW) {
@@ -2065,18 +1982,8 @@ __device__ int newton_direction_tile(CPR pr0, const Game& G0, DirLds<C>& L, doub
         ALG_PROF(1)
         // prefetch of the next step's record: issued after the register-hungry MFMA phase, landed by the end of the step
         double pre[RPL];
-        // (one-wavefront kernels only: in the C5 loop kernel -- team of four -- the same change raised the SGPR spills from 13 to 34)
-        constexpr bool PRE2 = ALG_R6_SADDR >= 2 && C::NW == 1;
-        if constexpr (PRE2) {
-            // unconditional loads from clamped addresses off a scalar base (step 0 re-requests its own record, nothing lands it): the conditional
-            // form -- zeroed registers, two exec-masked branches, each re-reading the record offset from the kernel arguments -- drained vmcnt
-            // and exposed two scalar round trips per step
-            const int kp = __builtin_amdgcn_readfirstlane(k > 0 ? k - 1 : 0);
-            const double* const Rb = as_global(reinterpret_cast<const double*>(uniform_u64(reinterpret_cast<unsigned long long>(G.rec(pr) + (size_t)kp * R::LEN))));
-#pragma unroll
-            for (int q = 0; q < RPL; q++) { const int e = tid + q * BT; pre[q] = gld(Rb, e < R::LEN_SWEEP ? e : R::LEN_SWEEP - 1); }
-        }
-        else if (!HELP2 && k > 0) {                                  // (team of two: the helper wavefront fetches the record)
+        // (as unconditional clamped loads off a scalar base the prefetch was 0.7 ... 2 % slower at C2 / C4: profiles/r06_ab_saddr_prefetch_*.txt)
+        if (!HELP2 && k > 0) {                                  // (team of two: the helper wavefront fetches the record)
 #pragma unroll
             for (int q = 0; q < RPL; q++) { const int e = tid + q * BT; pre[q] = e < R::LEN_SWEEP ? gld(G.rec(pr) + (size_t)(k - 1) * R::LEN, e) : 0.0; }
         }
@@ -2109,8 +2016,7 @@ __device__ int newton_direction_tile(CPR pr0, const Game& G0, DirLds<C>& L, doub
             const double* Pr = &L.bw.Pm[yp * n * LDP + yr * LDP];
             const double rdl = Rc[R::RD + yr];
             double a = Pr[n];
-            if constexpr (rowdot_split_v<C> && ALG_R6_ROWDOT_CHAINS > 2) rowdot_dpp_chains<n, ALG_R6_ROWDOT_CHAINS, (rowdot_group_v<C> < n ? rowdot_group_v<C> : n)>(a, rdl, [&](int c) { return Pr[c]; });
-            else if constexpr (rowdot_split_v<C>) rowdot_dpp_split<n, (rowdot_group_v<C> < n ? rowdot_group_v<C> : n)>(a, rdl, [&](int c) { return Pr[c]; });
+            if constexpr (rowdot_split_v<C>) rowdot_dpp_split<n, (rowdot_group_v<C> < n ? rowdot_group_v<C> : n)>(a, rdl, [&](int c) { return Pr[c]; });
             else rowdot_dpp_g<n, (rowdot_group_v<C> < n ? rowdot_group_v<C> : n)>(a, rdl, [&](int c) { return Pr[c]; });
             if (!GFUSE && (ty & 15) < n) L.bw.t[yp * n + yr] = a;
             // split recursion: y_i takes the place of s_i (this lane was its only reader): column n of [P_i A_k | y_i] in the next step
@@ -2229,18 +2135,13 @@ __device__ int newton_direction_tile(CPR pr0, const Game& G0, DirLds<C>& L, doub
         // meet stores that were just issued; measured neutral, the phase profile shows no exposed wait either way)
         asm volatile("" ::: "memory");
         if (!HELP2 && tw == 0 && rhsl) {
-#if ALG_R6_SADDR
             // (the step's base address as a scalar pair, ONE lane offset, the m entries of the column at immediate offsets: the compiler keeps the game's
-            // base pointers in VGPRs once the scalar file is full, and every store then paid two 64-bit vector adds, a copy and the offset's reload)
+            // base pointers in VGPRs once the scalar file is full, and every store then paid two 64-bit vector adds, a copy and the offset's reload.
+            // With the forward sweep's prefetches: C2 +1.5 ... 2.6 %, profiles/r06_ab_saddr_*.txt)
             double* const Kg = reinterpret_cast<double*>(uniform_u64(reinterpret_cast<unsigned long long>(G.kgain(pr) + (size_t)k * NK)));
             const unsigned ko = goff((cidx - m) * m);
 #pragma unroll
             for (int c = 0; c < m; c++) *reinterpret_cast<double*>(reinterpret_cast<char*>(as_global(Kg) + c) + ko) = col[c];
-#else
-            double* __restrict__ Kg = G.kgain(pr) + (size_t)k * NK;
-#pragma unroll
-            for (int c = 0; c < m; c++) gst(Kg, (cidx - m) * m + c, col[c]);
-#endif
         }
         bsync();
         ALG_PROF(6)

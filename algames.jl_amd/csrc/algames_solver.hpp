@@ -60,11 +60,8 @@ __device__ __forceinline__ RecScalars push_stats(CPR pr0, const Game& G0, const 
     return r;
 }
 // dual = true (fused kernels only, round 6): this record! is the one that follows dual_update! + penalty_update! in newton_solve!
-// (solver_methods.jl:57-61, then :73 of the next outer iteration) and performs them on the way (assemble_phase_a, DUAL)
-#ifndef ALG_R6_DUALREC
-#define ALG_R6_DUALREC 1        // A/B switch (tests/probes/build_variant.sh): 0 = dual_penalty_update as a pass of its own, as until round 5
-#endif
-template <class C> inline constexpr bool dual_in_record_v = AsmLds<C>::FUSED && ALG_R6_DUALREC != 0;
+// (solver_methods.jl:57-61, then :73 of the next outer iteration) and performs them on the way (phase_a_pos_item, DUAL)
+// (the other kernels keep dual_penalty_update as a pass of its own)
 template <class C>
 __device__ __forceinline__ RecScalars make_record(CPR pr, const Game& G, Lds<C>& L, double delta, int outer, double jreg, alg_record* out, bool dual = false) {
     ResOut ro;
@@ -181,9 +178,9 @@ __device__ __forceinline__ int inner_iteration(CPR pr0, Game& G_, Lds<C>& L, int
     iter_clock_start(pr, G_);                    // @elapsed begins (solver_methods.jl:40); record! below still reads the previous t_elap
     RecScalars rs;                                                         // :73-76 (regularisation term is zero at pdtraj)
     // *cache_valid: 1 = the accepted trial of the previous iteration is this record!; 2 = the dual / penalty update of the previous outer
-    // iteration is still due and rides on this record! pass (dual_in_record_v)
+    // iteration is still due and rides on this record! pass (fused kernels)
     if (cache_valid && *cache_valid == 1) { ResOut cro; tcache_load(pr, G, cro); rs = push_stats(pr, G, cro, Delta, k, info ? &info->rec : nullptr); }
-    else rs = make_record<C>(pr, G, L, Delta, k, reg, info ? &info->rec : nullptr, dual_in_record_v<C> && cache_valid && *cache_valid == 2);
+    else rs = make_record<C>(pr, G, L, Delta, k, reg, info ? &info->rec : nullptr, AsmLds<C>::FUSED && cache_valid && *cache_valid == 2);
     if (cache_valid) *cache_valid = 0;
     Delta = 0.0;                                                           // :79
     auto finish = [&](int status, int flow) { if (info && lane0) { info->status = status; info->control_flow = flow; } iter_clock_stop(pr, G_); return status | (flow << 8); };
@@ -244,7 +241,7 @@ __device__ void dual_penalty_update(CPR pr0, const Game& G0) {
             const double d0 = x[i] - x[j], d1 = x[P + i] - x[P + j], R = ALG_SCEN_AT(C, pr, G, ca_pair_r, SC_CAR, i * MAXP + j);
             double s2 = pair_dist2(d0, d1);
             if constexpr (C::PD == 3) { const double d2 = pr.ca_dim == 3 ? x[2 * P + i] - x[2 * P + j] : 0.0; s2 = __builtin_fma(d2, d2, s2); }
-            const double c = ca_value((double)((pr.ca_mask[i] >> j) & 1u), R, s2);      // (the roundings of assemble_phase_a: its DUAL form performs this very update)
+            const double c = ca_value((double)((pr.ca_mask[i] >> j) & 1u), R, s2);      // (the roundings of phase_a_pos_item: its DUAL form performs this very update)
             G.vals(pr)[e] = c;
             G.lam(pr)[e] = dual_ascent(G.lam(pr)[e], o.alphax_dual[i], G.mu(pr)[e], c, o.lambda_max);
         }
@@ -434,7 +431,7 @@ __device__ __forceinline__ void settle_traj(CPR pr, Game& G) {
 
 // penalty_update! scales mu of EVERY row of the constraint arena, including the rows of constraint kinds the problem does not have
 // (no collision avoidance / no control bounds: their rows exist in the layout, nothing reads them).  The record! pass that carries the
-// dual update (dual_in_record_v) visits the rows that exist; the others receive the solve's `nup` scalings here, once, in the same
+// dual update (fused kernels) visits the rows that exist; the others receive the solve's `nup` scalings here, once, in the same
 // order of operations -- the arena ends up bit-identical to dual_penalty_update's.
 template <class C>
 __device__ void penalty_update_unused_rows(CPR pr0, const Game& G0, int nup) {
@@ -473,7 +470,7 @@ __device__ __forceinline__ void handoff_park(CPR pr0, Game& G, int k, int l, int
     game_sync();
     // the scalings of mu that the fused dual updates deferred for the rows of absent constraint kinds: everything behind this point runs
     // dual_penalty_update on ALL rows (the team kernels are not fused kernels)
-    if constexpr (dual_in_record_v<C>) penalty_update_unused_rows<C>(pr0, G, (k - 1) - (cache_valid == 2 ? 1 : 0));
+    if constexpr (AsmLds<C>::FUSED) penalty_update_unused_rows<C>(pr0, G, (k - 1) - (cache_valid == 2 ? 1 : 0));
     CPR pr = phase_params(pr0);
     if (phase_lane() == 0) {
         const Game H = G.fresh();
@@ -509,7 +506,7 @@ __device__ __forceinline__ void newton_solve(CPR pr, Game& G, Lds<C>& L, int ini
         const int z0 = (int)uni(tc[TC_HO_ZO]);
         if (z0 != 0) { G.zo[1] = G.zo[0]; G.zo[0] = z0; }
         game_sync();
-        if (cv0 == 2 && !dual_in_record_v<C>) {                              // the dual / penalty update the parked kernel left to its next record!
+        if (cv0 == 2 && !AsmLds<C>::FUSED) {                              // the dual / penalty update the parked kernel left to its next record!
             dual_penalty_update<C>(pr, G);
             game_sync();
             cv0 = 0;
@@ -545,7 +542,7 @@ __device__ __forceinline__ void newton_solve(CPR pr, Game& G, Lds<C>& L, int ini
         const bool first = HO == 2 && k == k0;                             // the outer iteration a resumed game re-enters
         int LS_count = first ? ls0 : 0;
         // fused kernels: every outer iteration but the first begins behind a dual / penalty update, which its first record! performs (2)
-        int cache_valid = first ? cv0 : ((dual_in_record_v<C> && k > 1) ? 2 : 0);
+        int cache_valid = first ? cv0 : ((AsmLds<C>::FUSED && k > 1) ? 2 : 0);
         for (int l = first ? l0 : 1; l <= o.inner_iter; l++) {             // :38
             if constexpr (HO == 1) {
                 if (started >= budget) { handoff_park<C>(pr, G, k, l, LS_count, cache_valid, Delta); return; }
@@ -568,13 +565,13 @@ __device__ __forceinline__ void newton_solve(CPR pr, Game& G, Lds<C>& L, int ini
         const int convu = __builtin_amdgcn_readfirstlane((int)conv);
         if (convu && phase_lane() == 0) stk->converged = 1;          // written where it is decided (one loop-carried scalar less)
         if (k == oc.outer_iter || convu) break;                            // :49-55
-        if constexpr (!dual_in_record_v<C>) {
+        if constexpr (!AsmLds<C>::FUSED) {
             dual_penalty_update<C>(pr, G);                                 // :57-61
             game_sync();
         }                                                                  // (fused kernels: in the first record! of outer iteration k + 1)
     }
     game_sync();
-    if constexpr (dual_in_record_v<C>) penalty_update_unused_rows<C>(pr, G, out - 1);
+    if constexpr (AsmLds<C>::FUSED) penalty_update_unused_rows<C>(pr, G, out - 1);
     // :63 record! at the final iterate.  When the solver left its loops at the optimality test of an inner iteration (the usual
     // exit) that iteration's record! was made at this very iterate with these very multipliers: the same numbers, so the
     // assemble pass is not repeated, the record is pushed again (with the Delta and outer index this call passes)
