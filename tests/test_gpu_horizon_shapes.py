@@ -51,14 +51,15 @@ def horizons(model, p, d=2):
     return sorted(set(range(2, 19)) | edge)
 
 
-def family(make, model, p, d, N, B=4, seed=0, turn=0.5, wall=False):
+def family(make, model, p, d, N, B=4, seed=0, turn=0.5, wall=False, spherical=False):
     """The short-horizon family on the Batch / OracleBatch API: make(model, p, N, dt, B, d) -> batch.  Players start on a circle of radius
     0.4 +- 0.05 at angles 2 pi i / p +- 0.3 and go to the point at radius 0.6 on the far side, rotated by 0.4 rad (d = 3: heights
     +- 0.1 on top; d = 1: the x coordinates of these points for two players, who meet head-on and stop against each other; more players on a
     line that do the same diverge in the oracle itself -- |oracle - arbiter| up to 1e4 -- so they keep their order, 0.5 apart, and go to targets
     0.15 apart, closer than the pair radius 0.26); unicycles and bicycles head for the target +- `turn` rad at speed 0.5.  Q = 10, R = 0.1,
     uf = 0, collision cost of radius 1.0 and mu 2.0, collision avoidance 0.13 per player, control bounds +- 0.8.  wall: one far-away wall
-    (never active) that switches the handle to the extended-constraint kernels."""
+    (never active) that switches the handle to the extended-constraint kernels.  spherical (d = 3): the collision avoidance measures the
+    distance in x, y, z (add_spherical_collision_avoidance) instead of x, y."""
     rng = np.random.default_rng([seed, model, p, d, N])
     b = make(model, p, N, DT, B, d)
     ni, mi = b.n // p, b.mi
@@ -89,7 +90,7 @@ def family(make, model, p, d, N, B=4, seed=0, turn=0.5, wall=False):
     b.set_options(**OPTS)
     if p > 1:
         b.add_collision_cost(np.full(p, 1.0), np.full(p, 2.0))
-        b.add_collision_avoidance(np.full(p, 0.13))
+        (b.add_spherical_collision_avoidance if spherical else b.add_collision_avoidance)(np.full(p, 0.13))
     b.add_control_bound(np.full(b.m, 0.8), np.full(b.m, -0.8))
     if wall:
         b.add_wall_constraint([5.0], [5.0], [6.0], [5.0], [0.0], [1.0])
@@ -121,12 +122,20 @@ TUNED = {(DI, 4, 2): dict(seed=1), (DI, 2, 3): dict(seed=2), (UNI, 1, 2): dict(t
 _REF = {}
 
 
-def reference(orc, model, p, d, N, wall=False, kind=""):
-    """The oracle (kind "") or the long-double arbiter ("x") of family(model, p, d, N), B = 4, seed 0: built once per session, solved on first use."""
-    key = (model, p, d, N, wall, kind)
-    if key not in _REF:
-        _REF[key] = Solved(family(lambda *a: orc.OracleBatch(*a[:5], d=a[5], kind=kind), model, p, d, N, wall=wall, **TUNED.get((model, p, d), {})))
-    return _REF[key]
+def _oracle_family(orc, cfg, N, wall, kind, build):
+    """family(*cfg, N) -- or another family, build(make, model, p, d, N) -- on the oracle (kind "") or the long-double arbiter ("x")"""
+    make = lambda *a: orc.OracleBatch(*a[:5], d=a[5], kind=kind)
+    return build(make, *cfg, N) if build else family(make, *cfg, N, wall=wall, **TUNED.get(tuple(cfg), {}))
+
+
+def reference(orc, model, p, d, N, wall=False, kind="", build=None, key=None):
+    """The oracle (kind "") or the long-double arbiter ("x") of family(model, p, d, N), B = 4, seed 0: built once per session, solved on first use.
+    build / key: another problem family, build(make, model, p, d, N) -> batch, cached under its own key."""
+    assert (build is None) == (key is None)
+    k = (key, model, p, d, N, wall, kind)
+    if k not in _REF:
+        _REF[k] = Solved(_oracle_family(orc, (model, p, d), N, wall, kind, build))
+    return _REF[k]
 
 
 def hip_family(alg, model, p, d, N, **kw):
@@ -167,11 +176,12 @@ def _note(shape, err):
     WORST[shape] = max(WORST.get(shape, 0.0), float(err))
 
 
-def _compare(g, orc, cfg, N, wall=False, tag=()):
+def _compare(g, orc, cfg, N, wall=False, tag=(), build=None, key=None):
     """g.newton_solve against the cached oracle of the same problem: test_gpu_fuzz._compare_solve with the arbiter (discrete history
     identical, 1e-8, else the arbiter rule; no game left out), then mu bit-equal and lambda <= 1e-6 relative on the games the oracle
-    converged (test_gpu_parity._assert_solve_parity).  Returns the worst |hip - oracle| over the games of status OK."""
-    o, x = reference(orc, *cfg, N, wall=wall), reference(orc, *cfg, N, wall=wall, kind="x")
+    converged (test_gpu_parity._assert_solve_parity).  Returns the worst |hip - oracle| over the games of status OK.  build / key: the
+    problem family g was built from, where it is not `family` (see reference)."""
+    o, x = reference(orc, *cfg, N, wall=wall, build=build, key=key), reference(orc, *cfg, N, wall=wall, kind="x", build=build, key=key)
     FZ._compare_solve(g, o, (cfg[0], cfg[1], N, DT) + tuple(tag), x=x)
     so = o.newton_solve()
     conv = so["converged"] == 1
@@ -368,11 +378,12 @@ def mpc_loop(b, steps=MPC_STEPS, fused=True):
     return it, cv, states
 
 
-def mpc_reference(orc, cfg, N, kind=""):
-    key = (cfg, N, kind)
-    if key not in _MPC_REF:
-        _MPC_REF[key] = mpc_loop(family(lambda *a: orc.OracleBatch(*a[:5], d=a[5], kind=kind), *cfg, N, **TUNED.get(cfg, {})))
-    return _MPC_REF[key]
+def mpc_reference(orc, cfg, N, kind="", build=None, key=None):
+    assert (build is None) == (key is None)
+    k = (key, cfg, N, kind)
+    if k not in _MPC_REF:
+        _MPC_REF[k] = mpc_loop(_oracle_family(orc, cfg, N, False, kind, build))
+    return _MPC_REF[k]
 
 
 @pytest.mark.parametrize("cfg,nw", MPC_CONFIGS, ids=lambda v: _name(v) or ("w1" if v else "team"))

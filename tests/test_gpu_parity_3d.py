@@ -229,13 +229,9 @@ def test_3d_receding_horizon_and_ibr_solve_parity(alg, orc):
     assert np.abs(zg - zo).max() <= 1e-7 * max(1.0, np.abs(zo).max())
 
 
-@pytest.mark.parametrize("model,p,N", [(DI, 2, 7), (3, 2, 5)])
-def test_per_player_wall3d_and_cylinder_parity(alg, orc, model, p, N):
-    """add_wall_constraint!(game_con, i, walls::Vector{Wall3D}) / (game_con, i, walls::Vector{CylinderWall})
-    (constraints_methods.jl:208-247, 256-299): DIFFERENT 3-D wall / cylinder sets per player with one shared entry each, HIP path vs
-    oracle on a DoubleIntegrator (d = 3) and a Quadrotor game: residual, Jacobian, direction, an inner iteration, the dual / penalty
-    update and a short full solve; the rows of a player an entry does not constrain stay inert."""
-    B = 3
+def _per_player_pair(alg, orc, model, p, N, B=3):
+    """The per-player Wall3D / cylinder problem: both panels for player 0 and the slanted one for the last player (one shared entry),
+    cylinders 0 (z axis), 1 (x axis) for the last player and 1, 2 (y axis) for player 0; random iterate, multipliers and penalties."""
     g = alg.Batch(alg.hip_lib(), model, p, N, 0.1, B, d=3)
     o = orc.OracleBatch(model, p, N, 0.1, B, d=3)
     rng = np.random.default_rng(33)
@@ -264,6 +260,17 @@ def test_per_player_wall3d_and_cylinder_parity(alg, orc, model, p, N):
     lam[rng.random((B, g.con_len)) < 0.3] = 0.0
     for b in (g, o):
         b.set_traj(z); b.set_con_duals(lam, mu)
+    return g, o
+
+
+@pytest.mark.parametrize("model,p,N", [(DI, 2, 7), (3, 2, 5)])
+def test_per_player_wall3d_and_cylinder_parity(alg, orc, model, p, N):
+    """add_wall_constraint!(game_con, i, walls::Vector{Wall3D}) / (game_con, i, walls::Vector{CylinderWall})
+    (constraints_methods.jl:208-247, 256-299): DIFFERENT 3-D wall / cylinder sets per player with one shared entry each, HIP path vs
+    oracle on a DoubleIntegrator (d = 3) and a Quadrotor game: residual, Jacobian, direction, an inner iteration, the dual / penalty
+    update and a short full solve; the rows of a player an entry does not constrain stay inert."""
+    B = 3
+    g, o = _per_player_pair(alg, orc, model, p, N, B)
     rg, ng = g.residual(0, 0.0); ro, no = o.residual(0, 0.0)
     assert np.abs(rg - ro).max() <= 1e-12 * (1 + np.abs(ro).max()) and np.allclose(ng, no, rtol=1e-13, atol=0)
     Jg, Jo = g.residual_jacobian(1e-3), o.residual_jacobian(1e-3)

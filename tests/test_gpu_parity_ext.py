@@ -282,12 +282,9 @@ def test_no_kernel_writes_outside_its_buffers(alg, case):
     assert _guards_ok(g) == 0
 
 
-@pytest.mark.parametrize("model,p,N", [(UNI, 3, 9), (BIC, 2, 8), (DI, 4, 6)])
-def test_per_player_wall_and_circle_parity(alg, orc, model, p, N):
-    """add_wall_constraint!(game_con, i, walls) / add_circle_constraint!(game_con, i, ...) (constraints_methods.jl:121-139, 161-187):
-    different sets for different players (one shared entry), HIP path vs oracle: residual, Jacobian, direction, an inner iteration,
-    the dual / penalty update and a short full solve."""
-    B = 3
+def _per_player_pair(alg, orc, model, p, N, B=3):
+    """The per-player wall / circle problem: walls 0, 1 for player 0 and walls 1, 2 for the last player (the second wall is one shared entry),
+    circle 0 for the last player and, with more than two players, circles 1, 0 for player 1; random iterate, multipliers and penalties."""
     g = alg.Batch(alg.hip_lib(), model, p, N, 0.1, B)
     o = orc.OracleBatch(model, p, N, 0.1, B)
     rng = np.random.default_rng(21)
@@ -310,6 +307,15 @@ def test_per_player_wall_and_circle_parity(alg, orc, model, p, N):
     lam[rng.random((B, g.con_len)) < 0.3] = 0.0
     for b in (g, o):
         b.set_traj(z); b.set_con_duals(lam, mu)
+    return g, o
+
+
+@pytest.mark.parametrize("model,p,N", [(UNI, 3, 9), (BIC, 2, 8), (DI, 4, 6)])
+def test_per_player_wall_and_circle_parity(alg, orc, model, p, N):
+    """add_wall_constraint!(game_con, i, walls) / add_circle_constraint!(game_con, i, ...) (constraints_methods.jl:121-139, 161-187):
+    different sets for different players (one shared entry), HIP path vs oracle: residual, Jacobian, direction, an inner iteration,
+    the dual / penalty update and a short full solve."""
+    g, o = _per_player_pair(alg, orc, model, p, N)
     rg, ng = g.residual(0, 0.0); ro, no = o.residual(0, 0.0)
     assert np.abs(rg - ro).max() <= 1e-12 * (1 + np.abs(ro).max()) and np.allclose(ng, no, rtol=1e-13, atol=0)
     Jg, Jo = g.residual_jacobian(1e-3), o.residual_jacobian(1e-3)
