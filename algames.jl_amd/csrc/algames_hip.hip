@@ -10,18 +10,14 @@
 #include <string>
 #include <vector>
 
-// every kernel instantiation lives in its own translation unit: the base configurations in algames_base.hip (compiled once per
-// entry; algames_base_scen.hip / algames_mw_scen.hip: their twins that read the game's scenario block), the EXT instantiations in
-// algames_ext_*.hip, the team kernels in algames_mw.hip, the dense-direction ones in theirs, the scheduled receding-horizon loops in algames_sched.hip
-// (a one-wavefront configuration has its kernels, its scheduled loop, its plant knot and its KKT solve -- algames_kkt.hip --, a team its kernels
+// every kernel instantiation lives in another translation unit: the base configurations and their twins that read the game's scenario block in
+// algames_base.hip (compiled once per entry and ext value), the team kernels in algames_mw.hip (once per ext value), every other family's
+// kernels, and every family's scheduled receding-horizon loops and KKT solves, in algames_unit.hip (once per list and kernel set)
+// (a one-wavefront configuration has its kernels, its scheduled loop, its plant knot and its KKT solve, a team its kernels
 // and its scheduled loop)
 #define ALG_DECLARE_ONE_(M, P, D, E) ALG_DECLARE_KERNELS(M, P, D, E) ALG_DECLARE_SCHED(M, P, D, E) ALG_DECLARE_PLANT(M, P, D, E) ALG_DECLARE_KKT(M, P, D, E)
 #define ALG_DECLARE_TEAM_(M, P, D, E, W) ALG_DECLARE_MW(M, P, D, E, W) ALG_DECLARE_SCHED_MW(M, P, D, E, W)
-ALG_CFGS_BASE(ALG_DECLARE_ONE_)
-ALG_CFGS_BASE_SCEN(ALG_DECLARE_ONE_)
-ALG_CFGS_EXT(ALG_DECLARE_ONE_)
-ALG_CFGS_DENSE(ALG_DECLARE_ONE_)
-ALG_CFGS_DI1(ALG_DECLARE_ONE_)
+ALG_CFGS_ONE(ALG_DECLARE_ONE_)
 ALG_CFGS_MW(ALG_DECLARE_TEAM_)
 ALG_CFGS_MW_SCEN(ALG_DECLARE_TEAM_)
 ALG_CFGS_MW_DENSE(ALG_DECLARE_TEAM_)
@@ -172,7 +168,7 @@ void recount_con(Params& p) {
 template <class F>
 bool dispatch_cfg(const Params& p, int ext, F&& f) {
 #define X(M, P, D, E) if (p.model == (M) && p.p == (P) && p.d == (D) && ext == (E)) { f(Cfg<M, P, D, E>{}); return true; }
-    ALG_CFGS_BASE(X) ALG_CFGS_BASE_SCEN(X) ALG_CFGS_EXT(X) ALG_CFGS_DENSE(X) ALG_CFGS_DI1(X)
+    ALG_CFGS_ONE(X)
 #undef X
     return false;
 }

@@ -1,8 +1,8 @@
 // algames_kernels.hpp -- the __global__ entry points (one workgroup = one wavefront = one game) and the list of compiled
-// (model, p, d, ext) instantiations.  The base instantiations live in algames_hip.hip; the EXT ones (bicycle model, state
-// bounds, walls, circles) are explicitly instantiated in algames_ext_*.hip so that the translation units build in parallel.
-// ext = 2 (Cfg::SCEN without Cfg::EXT): the base kernels with the scenario numbers read from the game's block (algames_base_scen.hip,
-// algames_mw_scen.hip).
+// (model, p, d, ext) instantiations, as lists ALG_CFGS_*(X).  Every list is explicitly instantiated in translation units of its own, so
+// that they build in parallel: algames_unit.hip applies one instantiation macro to one list, both named by the build (the table of
+// families in __graft_entry__.py); algames_base.hip holds one base configuration per unit, algames_mw.hip the teams and their hand-off.
+// ext = 2 (Cfg::SCEN without Cfg::EXT): the base kernels with the scenario numbers read from the game's block.
 #pragma once
 #include "algames_device.hpp"
 
@@ -251,7 +251,7 @@ __global__ void __launch_bounds__(C::NT, mpc_loop_wpe<C>) k_mpc_loop(Params pr_a
 // The receding-horizon loop with a SCHEDULE (alg_mpc_set_schedule): per game and per MPC step values of the numbers that may differ per
 // game -- the kinds of the scenario block and the LQR targets xf / uf.  A sibling of k_mpc_loop, not one more argument of it: k_mpc_loop's
 // source, and with it the binary of every unscheduled loop, stays what it was; the siblings live in translation units of
-// their own (algames_sched.hip) and are launched only while the handle carries a schedule, a disturbance or a plant (alg_mpc_set_plant), or the
+// their own (ALG_DEFINE_SCHED*) and are launched only while the handle carries a schedule, a disturbance or a plant (alg_mpc_set_plant), or the
 // call asks for a log (alg_mpc_solve_log): the sibling is the loop with per-step phases.
 // The schedule sits in device memory in compact form, rows x B x len doubles per kind, with a table of len block offsets per kind (the host's
 // scen_map; ALG_SCHED_TO_LQR marks an offset into the game's LQR block, a negative entry is skipped like alg_set_scenario_data skips it).
@@ -589,27 +589,26 @@ __global__ void __launch_bounds__(WAVE, C::WPE) k_kkt_solve(Params pr_arg, doubl
 // ------------------------------------------------------------------------------------------------
 // Instantiation lists: X(model, p, d, ext)
 // ------------------------------------------------------------------------------------------------
-#define ALG_CFGS_BASE(X)                                    \
-    X(ALG_MODEL_DOUBLE_INTEGRATOR, 1, 2, 0)                  \
-    X(ALG_MODEL_DOUBLE_INTEGRATOR, 2, 2, 0)                  \
-    X(ALG_MODEL_DOUBLE_INTEGRATOR, 3, 2, 0)                  \
-    X(ALG_MODEL_DOUBLE_INTEGRATOR, 4, 2, 0)                  \
-    X(ALG_MODEL_DOUBLE_INTEGRATOR, 2, 3, 0)                  \
-    X(ALG_MODEL_UNICYCLE, 1, 2, 0)                           \
-    X(ALG_MODEL_UNICYCLE, 2, 2, 0)                           \
-    X(ALG_MODEL_UNICYCLE, 3, 2, 0)                           \
-    X(ALG_MODEL_UNICYCLE, 4, 2, 0)
-// The same nine with the scenario numbers taken from the game's block (Cfg::SCEN, ext = 2; alg_set_scenario_kernels): algames_base_scen.hip
-#define ALG_CFGS_BASE_SCEN(X)                               \
-    X(ALG_MODEL_DOUBLE_INTEGRATOR, 1, 2, 2)                  \
-    X(ALG_MODEL_DOUBLE_INTEGRATOR, 2, 2, 2)                  \
-    X(ALG_MODEL_DOUBLE_INTEGRATOR, 3, 2, 2)                  \
-    X(ALG_MODEL_DOUBLE_INTEGRATOR, 4, 2, 2)                  \
-    X(ALG_MODEL_DOUBLE_INTEGRATOR, 2, 3, 2)                  \
-    X(ALG_MODEL_UNICYCLE, 1, 2, 2)                           \
-    X(ALG_MODEL_UNICYCLE, 2, 2, 2)                           \
-    X(ALG_MODEL_UNICYCLE, 3, 2, 2)                           \
-    X(ALG_MODEL_UNICYCLE, 4, 2, 2)
+// The nine base configurations, by their ext column E: 0 = the scenario numbers are kernel constants, 2 = they are read from the game's
+// block (Cfg::SCEN without Cfg::EXT; alg_set_scenario_kernels).  The kernels of entry k live in a unit of their own (algames_base.hip), the
+// scheduled loops and the KKT solves in one unit per half.
+#define ALG_CFGS_BASE_DI_E(X, E)                            \
+    X(ALG_MODEL_DOUBLE_INTEGRATOR, 1, 2, E)                  \
+    X(ALG_MODEL_DOUBLE_INTEGRATOR, 2, 2, E)                  \
+    X(ALG_MODEL_DOUBLE_INTEGRATOR, 3, 2, E)                  \
+    X(ALG_MODEL_DOUBLE_INTEGRATOR, 4, 2, E)                  \
+    X(ALG_MODEL_DOUBLE_INTEGRATOR, 2, 3, E)
+#define ALG_CFGS_BASE_UNI_E(X, E)                           \
+    X(ALG_MODEL_UNICYCLE, 1, 2, E)                           \
+    X(ALG_MODEL_UNICYCLE, 2, 2, E)                           \
+    X(ALG_MODEL_UNICYCLE, 3, 2, E)                           \
+    X(ALG_MODEL_UNICYCLE, 4, 2, E)
+#define ALG_CFGS_BASE_DI(X) ALG_CFGS_BASE_DI_E(X, 0)
+#define ALG_CFGS_BASE_UNI(X) ALG_CFGS_BASE_UNI_E(X, 0)
+#define ALG_CFGS_BASE_SCEN_DI(X) ALG_CFGS_BASE_DI_E(X, 2)
+#define ALG_CFGS_BASE_SCEN_UNI(X) ALG_CFGS_BASE_UNI_E(X, 2)
+#define ALG_CFGS_BASE(X) ALG_CFGS_BASE_DI(X) ALG_CFGS_BASE_UNI(X)
+#define ALG_CFGS_BASE_SCEN(X) ALG_CFGS_BASE_SCEN_DI(X) ALG_CFGS_BASE_SCEN_UNI(X)
 #define ALG_CFGS_EXT_DI(X)                                  \
     X(ALG_MODEL_DOUBLE_INTEGRATOR, 1, 2, 1)                  \
     X(ALG_MODEL_DOUBLE_INTEGRATOR, 2, 2, 1)                  \
@@ -627,7 +626,7 @@ __global__ void __launch_bounds__(WAVE, C::WPE) k_kkt_solve(Params pr_arg, doubl
     X(ALG_MODEL_BICYCLE, 4, 2, 1)
 #define ALG_CFGS_EXT_DI3(X)                                 \
     X(ALG_MODEL_DOUBLE_INTEGRATOR, 2, 3, 1)
-// QuadrotorGame (quadrotor.jl:22: p <= 4), dense Newton direction (algames_quad.hip)
+// QuadrotorGame (quadrotor.jl:22: p <= 4), dense Newton direction
 #define ALG_CFGS_QUAD(X)                                    \
     X(ALG_MODEL_QUADROTOR, 1, 3, 0)                          \
     X(ALG_MODEL_QUADROTOR, 2, 3, 0)                          \
@@ -638,7 +637,7 @@ __global__ void __launch_bounds__(WAVE, C::WPE) k_kkt_solve(Params pr_arg, doubl
     X(ALG_MODEL_QUADROTOR, 2, 3, 1)                          \
     X(ALG_MODEL_QUADROTOR, 3, 3, 1)                          \
     X(ALG_MODEL_QUADROTOR, 4, 3, 1)
-// DoubleIntegrator in three dimensions with p = 1, 3, 4 (n = 6, 18, 24: dense Newton direction; algames_di3.hip)
+// DoubleIntegrator in three dimensions with p = 1, 3, 4 (n = 6, 18, 24: dense Newton direction)
 #define ALG_CFGS_DI3D(X)                                    \
     X(ALG_MODEL_DOUBLE_INTEGRATOR, 1, 3, 0)                  \
     X(ALG_MODEL_DOUBLE_INTEGRATOR, 3, 3, 0)                  \
@@ -648,13 +647,13 @@ __global__ void __launch_bounds__(WAVE, C::WPE) k_kkt_solve(Params pr_arg, doubl
     X(ALG_MODEL_DOUBLE_INTEGRATOR, 4, 3, 1)
 // DoubleIntegratorGame(p, d = 1) (double_integrator.jl:13-25 takes any d; round 6): n = 2 p, m = p.  px[i] = (i, i + p) is (position, velocity) of
 // player i here -- the reference's index sets do not depend on d -- and the collision terms act on that pair as they do in the reference.
-// p = 2, 4 take the tile path, p = 1, 3 (n = 2, 6) the dense direction; base constraint set (algames_di1.hip)
+// p = 2, 4 take the tile path, p = 1, 3 (n = 2, 6) the dense direction; base constraint set
 #define ALG_CFGS_DI1(X)                                     \
     X(ALG_MODEL_DOUBLE_INTEGRATOR, 1, 1, 0)                  \
     X(ALG_MODEL_DOUBLE_INTEGRATOR, 2, 1, 0)                  \
     X(ALG_MODEL_DOUBLE_INTEGRATOR, 3, 1, 0)                  \
     X(ALG_MODEL_DOUBLE_INTEGRATOR, 4, 1, 0)
-// Five and six players (n = 20 / 24: dense Newton direction; algames_p5.hip, algames_p6.hip).  The reference itself caps p at 10 (options.jl:68)
+// Five and six players (n = 20 / 24: dense Newton direction).  The reference itself caps p at 10 (options.jl:68)
 #define ALG_CFGS_P5(X)                                      \
     X(ALG_MODEL_DOUBLE_INTEGRATOR, 5, 2, 0)                  \
     X(ALG_MODEL_DOUBLE_INTEGRATOR, 5, 2, 1)                  \
@@ -669,8 +668,8 @@ __global__ void __launch_bounds__(WAVE, C::WPE) k_kkt_solve(Params pr_arg, doubl
     X(ALG_MODEL_BICYCLE, 6, 2, 1)
 #define ALG_CFGS_P56(X) ALG_CFGS_P5(X) ALG_CFGS_P6(X)
 // Seven to nine players (round 6; n = 28 ... 36, m = 14 ... 18: the dense direction with the value matrices of all players LDS-resident --
-// 65 / 93 / 128 KB of the CU's 160, one game per CU; algames_p7.hip ... algames_p9.hip).  Ten players (the reference's cap, options.jl:68;
-// algames_p10.hip): 131 KB of value matrices, the step's workspace in the TIGHT layout of DirLds<C, true> -- 161 KB.
+// 65 / 93 / 128 KB of the CU's 160, one game per CU).  Ten players (the reference's cap, options.jl:68):
+// 131 KB of value matrices, the step's workspace in the TIGHT layout of DirLds<C, true> -- 161 KB.
 #define ALG_CFGS_PN(X, N)                                   \
     X(ALG_MODEL_DOUBLE_INTEGRATOR, N, 2, 0)                  \
     X(ALG_MODEL_DOUBLE_INTEGRATOR, N, 2, 1)                  \
@@ -684,6 +683,8 @@ __global__ void __launch_bounds__(WAVE, C::WPE) k_kkt_solve(Params pr_arg, doubl
 #define ALG_CFGS_P789(X) ALG_CFGS_P7(X) ALG_CFGS_P8(X) ALG_CFGS_P9(X) ALG_CFGS_P10(X)
 #define ALG_CFGS_DENSE(X) ALG_CFGS_QUAD(X) ALG_CFGS_QUAD_EXT(X) ALG_CFGS_DI3D(X) ALG_CFGS_P56(X) ALG_CFGS_P789(X)
 #define ALG_CFGS_EXT(X) ALG_CFGS_EXT_DI(X) ALG_CFGS_EXT_UNI(X) ALG_CFGS_EXT_BIC(X) ALG_CFGS_EXT_DI3(X)
+// every one-wavefront configuration of the library, in the order the host's declarations and dispatch_cfg walk them (algames_hip.hip)
+#define ALG_CFGS_ONE(X) ALG_CFGS_BASE(X) ALG_CFGS_BASE_SCEN(X) ALG_CFGS_EXT(X) ALG_CFGS_DENSE(X) ALG_CFGS_DI1(X)
 
 // every kernel of one instantiation; PREFIX is `template` (definition) or `extern template` (declaration)
 #define ALG_INSTANTIATE_KERNELS(PREFIX, M, P, D, E)                                                                        \
@@ -702,18 +703,15 @@ __global__ void __launch_bounds__(WAVE, C::WPE) k_kkt_solve(Params pr_arg, doubl
     PREFIX __global__ void k_mpc_loop<Cfg<M, P, D, E>>(Params, int, uint64_t, double*);
 // Team kernels (Cfg::NW wavefronts per game, small batches): X(model, p, d, ext, nw).  Only the fused solver and the fused
 // receding-horizon loop exist in this shape; the step-wise entry points always use one wavefront per game.
-#define ALG_CFGS_MW(X)                                      \
-    X(ALG_MODEL_DOUBLE_INTEGRATOR, 3, 2, 0, 4)               \
-    X(ALG_MODEL_UNICYCLE, 3, 2, 0, 4)                        \
-    X(ALG_MODEL_UNICYCLE, 4, 2, 0, 2)                        \
-    X(ALG_MODEL_UNICYCLE, 4, 2, 0, 4)
-// ... and their twins that read the game's scenario block (algames_mw_scen.hip)
-#define ALG_CFGS_MW_SCEN(X)                                 \
-    X(ALG_MODEL_DOUBLE_INTEGRATOR, 3, 2, 2, 4)               \
-    X(ALG_MODEL_UNICYCLE, 3, 2, 2, 4)                        \
-    X(ALG_MODEL_UNICYCLE, 4, 2, 2, 2)                        \
-    X(ALG_MODEL_UNICYCLE, 4, 2, 2, 4)
-// Team kernels of the dense-direction configurations (algames_mw_dense.hip): where the LDS footprint leaves room for few
+#define ALG_CFGS_MW_E(X, E)                                 \
+    X(ALG_MODEL_DOUBLE_INTEGRATOR, 3, 2, E, 4)               \
+    X(ALG_MODEL_UNICYCLE, 3, 2, E, 4)                        \
+    X(ALG_MODEL_UNICYCLE, 4, 2, E, 2)                        \
+    X(ALG_MODEL_UNICYCLE, 4, 2, E, 4)
+#define ALG_CFGS_MW(X) ALG_CFGS_MW_E(X, 0)
+// ... and their twins that read the game's scenario block
+#define ALG_CFGS_MW_SCEN(X) ALG_CFGS_MW_E(X, 2)
+// Team kernels of the dense-direction configurations: where the LDS footprint leaves room for few
 // workgroups per CU at any batch size the automatic choice is the team of four regardless of the batch (team_width, algames_hip.hip)
 #define ALG_CFGS_MW_DENSE(X)                                \
     X(ALG_MODEL_QUADROTOR, 2, 3, 0, 4)                       \
@@ -731,14 +729,12 @@ __global__ void __launch_bounds__(WAVE, C::WPE) k_kkt_solve(Params pr_arg, doubl
     PREFIX __global__ void k_mpc_loop<Cfg<M, P, D, E, W>>(Params, int, uint64_t, double*);
 // Hand-off pairs: X(model, p, d, ext, w) = the budgeted one-wavefront kernel of (model, p, d, ext) parks, the team kernel of width w resumes
 // (base configurations that have a team kernel in ALG_CFGS_MW)
-#define ALG_CFGS_HANDOFF(X)                                 \
-    X(ALG_MODEL_DOUBLE_INTEGRATOR, 3, 2, 0, 4)               \
-    X(ALG_MODEL_UNICYCLE, 3, 2, 0, 4)                        \
-    X(ALG_MODEL_UNICYCLE, 4, 2, 0, 4)
-#define ALG_CFGS_HANDOFF_SCEN(X)                            \
-    X(ALG_MODEL_DOUBLE_INTEGRATOR, 3, 2, 2, 4)               \
-    X(ALG_MODEL_UNICYCLE, 3, 2, 2, 4)                        \
-    X(ALG_MODEL_UNICYCLE, 4, 2, 2, 4)
+#define ALG_CFGS_HANDOFF_E(X, E)                            \
+    X(ALG_MODEL_DOUBLE_INTEGRATOR, 3, 2, E, 4)               \
+    X(ALG_MODEL_UNICYCLE, 3, 2, E, 4)                        \
+    X(ALG_MODEL_UNICYCLE, 4, 2, E, 4)
+#define ALG_CFGS_HANDOFF(X) ALG_CFGS_HANDOFF_E(X, 0)
+#define ALG_CFGS_HANDOFF_SCEN(X) ALG_CFGS_HANDOFF_E(X, 2)
 #define ALG_INSTANTIATE_HO_PARK(PREFIX, M, P, D, E, W) PREFIX __global__ void k_newton_solve_ho<Cfg<M, P, D, E>>(Params, int, uint64_t, int);
 #define ALG_INSTANTIATE_HO_RESUME(PREFIX, M, P, D, E, W) PREFIX __global__ void k_newton_resume<Cfg<M, P, D, E, W, 0>>(Params);
 #define ALG_DEFINE_HO_RESUME(M, P, D, E, W) ALG_INSTANTIATE_HO_RESUME(template, M, P, D, E, W)
@@ -747,18 +743,18 @@ __global__ void __launch_bounds__(WAVE, C::WPE) k_kkt_solve(Params pr_arg, doubl
 #define ALG_DECLARE_MW(M, P, D, E, W) ALG_INSTANTIATE_MW(extern template, M, P, D, E, W)
 #define ALG_DEFINE_KERNELS(M, P, D, E) ALG_INSTANTIATE_KERNELS(template, M, P, D, E)
 #define ALG_DECLARE_KERNELS(M, P, D, E) ALG_INSTANTIATE_KERNELS(extern template, M, P, D, E)
-// The scheduled receding-horizon loops (k_mpc_loop_sched): one per loop kernel of the lists above, defined in algames_sched.hip
+// The scheduled receding-horizon loops (k_mpc_loop_sched): one per loop kernel of the lists above, in units of their own
 #define ALG_INSTANTIATE_SCHED(PREFIX, M, P, D, E) PREFIX __global__ void k_mpc_loop_sched<Cfg<M, P, D, E>>(Params, int, uint64_t, double*, MpcSched, MpcLoopLog, MpcPlant);
 #define ALG_INSTANTIATE_SCHED_MW(PREFIX, M, P, D, E, W) PREFIX __global__ void k_mpc_loop_sched<Cfg<M, P, D, E, W>>(Params, int, uint64_t, double*, MpcSched, MpcLoopLog, MpcPlant);
 #define ALG_DEFINE_SCHED(M, P, D, E) ALG_INSTANTIATE_SCHED(template, M, P, D, E)
 #define ALG_DECLARE_SCHED(M, P, D, E) ALG_INSTANTIATE_SCHED(extern template, M, P, D, E)
 #define ALG_DEFINE_SCHED_MW(M, P, D, E, W) ALG_INSTANTIATE_SCHED_MW(template, M, P, D, E, W)
-// The step-wise plant knot (k_mpc_plant_advance): one per one-wavefront configuration, defined in algames_plant.hip
+// The step-wise plant knot (k_mpc_plant_advance): one per one-wavefront configuration (ALG_CFGS_ONE), in a unit of their own
 #define ALG_INSTANTIATE_PLANT(PREFIX, M, P, D, E) PREFIX __global__ void k_mpc_plant_advance<Cfg<M, P, D, E>>(Params, int, MpcPlant);
 #define ALG_DEFINE_PLANT(M, P, D, E) ALG_INSTANTIATE_PLANT(template, M, P, D, E)
 #define ALG_DECLARE_PLANT(M, P, D, E) ALG_INSTANTIATE_PLANT(extern template, M, P, D, E)
 #define ALG_DECLARE_SCHED_MW(M, P, D, E, W) ALG_INSTANTIATE_SCHED_MW(extern template, M, P, D, E, W)
-// The KKT solves with many right-hand sides (k_kkt_solve): one per configuration that has a k_direction, defined in algames_kkt.hip
+// The KKT solves with many right-hand sides (k_kkt_solve): one per configuration that has a k_direction, in units of their own
 #define ALG_INSTANTIATE_KKT(PREFIX, M, P, D, E) PREFIX __global__ void k_kkt_solve<Cfg<M, P, D, E>>(Params, double, int, int, const double*, int, double*, int*);
 #define ALG_DEFINE_KKT(M, P, D, E) ALG_INSTANTIATE_KKT(template, M, P, D, E)
 #define ALG_DECLARE_KKT(M, P, D, E) ALG_INSTANTIATE_KKT(extern template, M, P, D, E)

@@ -14,13 +14,15 @@ FL="$FL -mllvm -amdgpu-inline-max-bb=100000"
 UNITS=${UNITS:-"base_0 base_1 base_2 base_3 base_4 base_5 base_6 base_7 base_8 ext_di ext_uni ext_bic ext_di3 mw"}
 J=0
 for u in $UNITS; do
-  case $u in
-    base_*) /opt/rocm/bin/hipcc $FL -DALG_BASE_SEL=${u#base_} -c $C/algames_base.hip -o $O/algames_$u.hip.o & ;;
-    *)      /opt/rocm/bin/hipcc $FL -c $C/algames_$u.hip -o $O/algames_$u.hip.o & ;;
-  esac
+  # the unit's source and defines: those of the build's table (__graft_entry__.HIP_UNITS)
+  read -r SRC DEFS < <(cd $R && python -c "import sys, __graft_entry__ as g; u = [u for u in g.HIP_UNITS if u[1] == 'algames_' + sys.argv[1]][0]; print(u[0], ' '.join(u[2]))" $u)
+  rm -f $O/algames_$u.hip.o
+  /opt/rocm/bin/hipcc $FL $DEFS -c $C/$SRC -o $O/algames_$u.hip.o &
   J=$((J+1)); if [ $J -ge 8 ]; then wait -n; J=$((J-1)); fi
 done
 wait
+# (a unit that failed to compile must not be replaced by the default build's object without a word)
+for u in $UNITS; do if [ ! -f $O/algames_$u.hip.o ]; then echo "build_variant.sh: unit $u did not compile" >&2; exit 1; fi; done
 OBJS=""
 for f in $D/*.hip.o; do b=$(basename $f); if [ -f $O/$b ]; then OBJS="$OBJS $O/$b"; else OBJS="$OBJS $f"; fi; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/algames.jl_amd/lib/variants/$NAME.so $OBJS

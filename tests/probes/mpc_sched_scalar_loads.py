@@ -2,7 +2,7 @@
 
     python tests/probes/mpc_sched_scalar_loads.py [--jobs 8] [--out profiles/mpc_log_scalar_loads.txt]
 
-Compiles the device side of every group of algames_sched.hip to assembly with the flags the build gives that group (hipcc
+Compiles the device side of every scheduled-loop unit of the build (__graft_entry__.KERNEL_SETS) to assembly with the unit's own flags (hipcc
 --cuda-device-only -S) and walks the body of every k_mpc_loop_sched kernel: each s_load_* / s_buffer_load_* is counted with the kind of
 its offset operand -- an immediate, or a register.  The phases of the loop store with vector stores; what the solver reads after them
 (scenario and LQR blocks, x0, x_1, the statistics) must therefore come through vector loads.  That holds if every scalar load of these
@@ -29,8 +29,8 @@ IMM = re.compile(r"^(0x[0-9a-fA-F]+|\d+)$")
 def assembly(unit, tmp):
     srcname, stem, extra = unit
     out = os.path.join(tmp, stem + ".s")
-    flags = [f for f in G.HIP_FLAGS if f not in ("--offload-compress", "-fPIC")]
-    subprocess.run(["/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc"] + flags + G._unit_flags(srcname, stem) + extra +
+    flags = [f for f in G.compile_flags(unit) if f not in ("--offload-compress", "-fPIC")]
+    subprocess.run(["/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc"] + flags +
                    ["--cuda-device-only", "-S", os.path.join(G.CSRC, srcname), "-o", out], check=True, stderr=subprocess.DEVNULL)
     return out
 
@@ -68,13 +68,13 @@ def main():
     ap.add_argument("--segment", type=int, default=2560, help="sizeof(MpcLoopSchedArgs)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    units = [u for u in G.HIP_UNITS if u[0] == "algames_sched.hip"]
+    units = G.KERNEL_SETS["sched"]
     kernels = {}
     with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(a.jobs) as ex:
         for path in ex.map(lambda u: assembly(u, tmp), units):
             kernels.update(scan(path))
     n_imm, n_reg, top = sum(k[0] for k in kernels.values()), sum(k[1] for k in kernels.values()), max(k[2] for k in kernels.values())
-    lines = ["k_mpc_loop_sched kernels: %d in %d groups of algames_sched.hip" % (len(kernels), len(units)),
+    lines = ["k_mpc_loop_sched kernels: %d in %d scheduled-loop units" % (len(kernels), len(units)),
              "scalar loads: %d, with an immediate offset %d (largest %d, kernel-argument segment %d bytes), with a register offset %d"
              % (n_imm + n_reg, n_imm, top, a.segment, n_reg)]
     lines += ["  register offset: %s (%d)" % (name, k[1]) for name, k in sorted(kernels.items()) if k[1]]

@@ -10,9 +10,9 @@ DI, UNI, BIC = 0, 1, 2
 CASES = [  # (model, p, N)
     (DI, 1, 6), (DI, 3, 10), (DI, 4, 6), (UNI, 1, 7), (UNI, 2, 12), (UNI, 3, 9), (UNI, 4, 6),
     (BIC, 1, 8), (BIC, 2, 12), (BIC, 3, 10), (BIC, 4, 6),
-    # five and six players (n = 20 / 24: dense Newton direction, algames_p5.hip / algames_p6.hip)
+    # five and six players (n = 20 / 24: dense Newton direction, ALG_CFGS_P5 / ALG_CFGS_P6)
     (DI, 5, 5), (DI, 6, 4), (UNI, 5, 5), (UNI, 6, 4), (BIC, 5, 5), (BIC, 6, 4),
-    # seven to ten players (round 6: algames_p7.hip ... algames_p10.hip; ten = the reference's cap, TIGHT LDS layout of the dense direction)
+    # seven to ten players (round 6: ALG_CFGS_P7 ... ALG_CFGS_P10; ten = the reference's cap, TIGHT LDS layout of the dense direction)
     (DI, 7, 4), (UNI, 8, 4), (BIC, 9, 4), (BIC, 7, 5), (DI, 9, 3), (UNI, 9, 4), (DI, 10, 4), (UNI, 10, 3), (BIC, 10, 4),
 ]
 ALL = ("cost", "avoid", "ctl", "sb", "wall", "circ")

@@ -61,13 +61,20 @@ def test_every_loop_kernel_has_a_scheduled_sibling_within_its_resources(alg):
 
 def test_the_scheduled_units_are_registered_with_the_build():
     import __graft_entry__ as ge
-    stems = [u[1] for u in ge.HIP_UNITS]
-    assert [s for s in stems if s.startswith("algames_sched_")] == ["algames_sched_%d" % k for k in range(21)]
-    assert os.path.exists(os.path.join(ge.CSRC, "algames_sched.hip"))
-    # the scheduled loops take the flags of the unit that holds their unscheduled siblings
-    assert ge._unit_flags("algames_sched.hip", "algames_sched_8") == ge._unit_flags("algames_mw.hip", "algames_mw")
-    assert ge._unit_flags("algames_sched.hip", "algames_sched_10") == ge._unit_flags("algames_quad.hip", "algames_quad")
-    assert ge._unit_flags("algames_sched.hip", "algames_sched_14") == ge._unit_flags("algames_p5.hip", "algames_p5")
+    sched = ge.KERNEL_SETS["sched"]
+    assert len(sched) == 21 and all(u in ge.HIP_UNITS and u[1].startswith("algames_sched_") for u in sched)
+    assert all(os.path.exists(os.path.join(ge.CSRC, u[0])) for u in sched)
+    # the scheduled loops take the flags of the unit that holds their unscheduled siblings: every family, every unit of it
+    for f in ge.FAMILIES:
+        mine, siblings = ge._sched_units(f), ge._kernel_units(f)
+        assert mine and siblings and all(u in sched for u in mine), f.name
+        for u in mine:
+            for v in siblings:
+                assert ge.unit_flags(u[1]) == ge.unit_flags(v[1]), (u[1], v[1])
+    assert sum(len(ge._sched_units(f)) for f in ge.FAMILIES) == 21
+    assert ge.unit_flags("algames_sched_mw") == ge.unit_flags("algames_mw") == ge.HIP_FLAGS_TILE
+    assert ge.unit_flags("algames_sched_quad") == ge.unit_flags("algames_quad") == ge.HIP_FLAGS_DENSE + ge.HIP_FLAGS_NOLSO
+    assert ge.unit_flags("algames_sched_p5") == ge.unit_flags("algames_p5") == ge.HIP_FLAGS_DENSE
 
 
 def test_python_kind_and_shape_validation(alg, orc):

@@ -58,6 +58,10 @@ def test_the_new_units_are_registered_with_the_build():
     import __graft_entry__ as ge
     stems = [u[1] for u in ge.HIP_UNITS]
     assert [s for s in stems if s.startswith("algames_base_scen_")] == ["algames_base_scen_%d" % k for k in range(9)]
-    assert "algames_mw_scen" in stems
+    # nine per-entry units with ext = 2, one per index, and the team unit with ext = 2
+    per_entry = [u for u in ge.HIP_UNITS if u[0] == "algames_base.hip" and "-DALG_BASE_EXT=2" in u[2]]
+    assert [u[1] for u in per_entry] == ["algames_base_scen_%d" % k for k in range(9)]
+    assert [u[2] for u in per_entry] == [["-DALG_BASE_SEL=%d" % k, "-DALG_BASE_EXT=2"] for k in range(9)]
+    assert ("algames_mw.hip", "algames_mw_scen", ["-DALG_MW_EXT=2"]) in ge.HIP_UNITS
     for src, stem, extra in ge.HIP_UNITS:
         assert os.path.exists(os.path.join(ge.CSRC, src)), src
