@@ -148,6 +148,9 @@ SIGNATURES = {
     "newton_solve_async": (C.c_int, [_P, C.c_int32, C.c_int64]),
     "get_stats": (C.c_int, [_P, _P]),
     "get_history": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _I]),
+    "set_history_profiles": (C.c_int, [_P, C.c_int32]),
+    "get_history_profiles": (C.c_int, [_P, _I]),
+    "get_history_vio": (C.c_int, [_P, C.c_int32, C.c_int32, _D, _D, _D, _D, _I]),
     "synchronize": (C.c_int, [_P]),
     "debug_check_guards": (C.c_int, [_P]),
     "ibr_solve_player": (C.c_int, [_P, C.c_int32, _P]),
@@ -170,7 +173,8 @@ SIGNATURES = {
 # Entry points a backend may lack (the CPU oracle has no per-game scenario data): bound when present; calling one that is absent
 # raises AlgamesError naming the backend.
 OPTIONAL = frozenset({"scenario_data_len", "set_scenario_data", "get_scenario_data", "set_scenario_kernels", "get_scenario_kernels",
-                      "mpc_set_schedule", "mpc_get_schedule", "mpc_solve_log", "mpc_set_plant", "mpc_get_plant", "mpc_plant_advance", "kkt_solve"})
+                      "mpc_set_schedule", "mpc_get_schedule", "mpc_solve_log", "mpc_set_plant", "mpc_get_plant", "mpc_plant_advance", "kkt_solve",
+                      "set_history_profiles", "get_history_profiles", "get_history_vio"})
 
 
 class AlgamesError(RuntimeError):
@@ -660,6 +664,33 @@ class Batch:
             import warnings
             warnings.warn(f"alg_get_history: game {game} made {made} records, the device history holds {cnt.value} (truncated)")
         return out[:cnt.value]
+
+    # ---- per-record violation profiles of the fused solve (alg_set_history_profiles) ---------
+    def set_history_profiles(self, max_records):
+        """newton_solve / newton_solve_async also store the four .vio vectors of every record they push, up to `max_records` records per
+        game (0 = off, the default: the buffer is freed).  Refused (AlgamesError) for seven to ten players, while a hand-off budget is
+        set, and for a buffer beyond 1 GiB; a backend without the entry point (the CPU oracle) raises AlgamesError."""
+        self.lib.check(self.lib.set_history_profiles(self.h, int(max_records)))
+
+    def get_history_profiles(self):
+        """Capacity in records per game (0 = off; also 0 on a backend without the entry point)."""
+        if "get_history_profiles" in self.lib.absent:
+            return 0
+        v = C.c_int32()
+        self.lib.check(self.lib.get_history_profiles(self.h, C.byref(v)))
+        return v.value
+
+    def get_history_vio(self, game, max_records=None):
+        """dict(dyn, con, sta, opt): the profiles of the records of one game's history, shapes (records, N-1 | N); row r belongs to record
+        r of get_history.  Zero rows with profiles off, and after any entry point other than newton_solve* has pushed records."""
+        cap = self.get_history_profiles() if max_records is None else int(max_records)
+        if cap > 0:                                 # (host arrays for the records the game made, not for the whole capacity)
+            cap = min(cap, max(int(self.get_stats()["records"][game]), 1))
+        K, N = self.N - 1, self.N
+        out = dict(dyn=np.zeros((cap, K)), con=np.zeros((cap, K)), sta=np.zeros((cap, N)), opt=np.zeros((cap, N)))
+        cnt = C.c_int32()
+        self.lib.check(self.lib.get_history_vio(self.h, int(game), cap, _dptr(out["dyn"]), _dptr(out["con"]), _dptr(out["sta"]), _dptr(out["opt"]), C.byref(cnt)))
+        return {k: v[:cnt.value] for k, v in out.items()}
 
     def synchronize(self):
         self.lib.check(self.lib.synchronize(self.h))

@@ -23,6 +23,11 @@ ALG_CFGS_MW_SCEN(ALG_DECLARE_TEAM_)
 ALG_CFGS_MW_DENSE(ALG_DECLARE_TEAM_)
 ALG_CFGS_HANDOFF(ALG_DECLARE_HO)
 ALG_CFGS_HANDOFF_SCEN(ALG_DECLARE_HO)
+// the solves with violation profiles (k_newton_solve_vio): every solve kernel but those of seven to ten players
+ALG_VIO_ONE(ALG_DECLARE_VIO)
+ALG_CFGS_MW(ALG_DECLARE_VIO_MW)
+ALG_CFGS_MW_SCEN(ALG_DECLARE_VIO_MW)
+ALG_CFGS_MW_DENSE(ALG_DECLARE_VIO_MW)
 
 __global__ void __launch_bounds__(WAVE) k_reset_con(Params pr_arg) {
     CPR pr = kernel_params();
@@ -235,6 +240,10 @@ struct Handle {
     int waves_per_game = 0;       // 0 = automatic (alg_set_waves_per_game)
     int handoff = 0;              // straggler hand-off budget (alg_set_handoff; 0 = off)
     int* d_ho = nullptr;          // its queue [count | game indices] (B + 1 ints)
+    // per-record violation profiles of the fused solve (alg_set_history_profiles): B x vio_max x (4 N - 2) doubles, an allocation of its own
+    double* d_vio = nullptr;
+    int vio_max = 0;              // capacity in records per game (0 = off)
+    bool vio_valid = false;       // the buffer holds the profiles of the Statistics history as it stands (set by alg_newton_solve*, cleared by every other entry point that pushes records)
     long long records_bound = 0;        // upper bound of the records the Statistics history holds since its last reset (one per record!)
     void* d_scratch = nullptr;    // grow-only scratch of the inspection entry points (dense Jacobians, MPC state logs)
     size_t scratch_bytes = 0;
@@ -406,8 +415,32 @@ int launch_fused(Handle* h, const char* what, One&& one, Team&& team) {
     if (!dispatch_team(h->pr, nw, [&](auto cfg, bool) { team(cfg); })) return fail(ALG_ERR_ARG, std::string(what) + ": nothing launched");
     return launch_check(what);
 }
+// the handle's configuration has a k_newton_solve_vio (alg_set_history_profiles)
+bool vio_supported(const Params& p) {
+    bool ok = false;
+    dispatch_cfg(p, p.ext, [&](auto cfg) { ok = vio_sibling_v<decltype(cfg)>; });
+    return ok;
+}
 int launch_newton_solve(Handle* h, int init, uint64_t game_id0) {
     const Params& pr = h->pr;
+    if (h->vio_max > 0) {
+        // profiles on: the sibling kernels, same shapes (no hand-off pair: alg_set_history_profiles and alg_set_handoff refuse each other)
+        double* const vio = h->d_vio; const int cap = h->vio_max;
+        return launch_fused(h, "k_newton_solve_vio (team)", [&]() -> int {
+            bool launched = false;
+            dispatch_cfg(pr, pr.ext, [&](auto cfg) {
+                using Cq = decltype(cfg);
+                if constexpr (vio_sibling_v<Cq>) {
+                    hipLaunchKernelGGL((history_vio::k_newton_solve_vio<Cq>), dim3(pr.B), dim3(WAVE), 0, h->stream, h->pr, init, game_id0, vio, cap);
+                    launched = true;
+                }
+            });
+            if (!launched) return fail(ALG_ERR_ARG, "k_newton_solve_vio: no kernel with violation profiles is compiled for this configuration");
+            return launch_check("k_newton_solve_vio");
+        }, [&](auto cfg) {
+            hipLaunchKernelGGL((history_vio::k_newton_solve_vio<decltype(cfg)>), dim3(pr.B), dim3(WAVE * decltype(cfg)::NW), 0, h->stream, h->pr, init, game_id0, vio, cap);
+        });
+    }
     return launch_fused(h, "k_newton_solve (team)", [&]() -> int {
         // straggler hand-off: the budgeted one-wavefront solve parks the games that exceed the budget, the team kernel resumes them
         // (the second launch covers the batch: its blocks past the queue's count leave at once -- no host round trip in between)
@@ -741,6 +774,7 @@ int mpc_solve_impl(const char* who, alg_handle* h, int32_t steps, int64_t game_i
     if (!h || steps < 1) return fail(ALG_ERR_ARG, std::string(who) + ": bad argument");
     int rc = use_device(H); if (rc) return rc;
     if (!H->x0_set || !H->lqr_set) return fail(ALG_ERR_STATE, std::string(who) + ": x0 / LQR data not set");
+    H->vio_valid = false;                         // the loop's solves push records without profiles
     const Params& p = H->pr;
     // one scratch allocation for all requested outputs: [states | controls | stats], every part 8-byte aligned; under a plant (alg_mpc_set_plant)
     // states and controls hold one row per plant knot, steps x hold of them
@@ -896,6 +930,7 @@ int alg_set_handoff(alg_handle* h, int32_t iters) {
     NEED_HANDLE("alg_set_handoff");
     if (iters < 0) return fail(ALG_ERR_ARG, "alg_set_handoff: iterations >= 0 (0 = off)");
     if (iters > 0) {
+        if (H->vio_max > 0) return fail(ALG_ERR_ARG, "alg_set_handoff: violation profiles are on (alg_set_history_profiles): the hand-off pair stores none");
         if (!dispatch_handoff(H->pr, [](auto, auto) {})) return fail(ALG_ERR_ARG, "alg_set_handoff: no hand-off kernel pair is compiled for this configuration (3-player DoubleIntegrator d = 2, 3- / 4-player Unicycle, base constraint set on the base kernels)");
         if (!H->d_ho) {
             int rc = use_device(H); if (rc) return rc;
@@ -1282,6 +1317,7 @@ int alg_record_stats(alg_handle* h, alg_record* rec) {
     if (!h || !rec) return fail(ALG_ERR_ARG, "alg_record_stats: null argument");
     int rc = use_device(H); if (rc) return rc;
     if ((rc = reserve_records(H, 1))) return rc;
+    H->vio_valid = false;
     LAUNCH(k_record, H->pr, H->d_rec);
     return d2h(H, rec, H->d_rec, sizeof(alg_record) * H->pr.B);
 }
@@ -1307,6 +1343,7 @@ int alg_newton_step(alg_handle* h, int32_t k_outer, int32_t l_inner, const doubl
     NEED_HANDLE("alg_newton_step");
     int rc = use_device(H); if (rc) return rc;
     if ((rc = reserve_records(H, 1))) return rc;  // one more record! in the shared Statistics history
+    H->vio_valid = false;
     const double* d_delta = nullptr;
     if (delta_in) { if ((rc = h2d(H, H->d_tmp, delta_in, sizeof(double) * H->pr.B))) return rc; d_delta = H->d_tmp; }
     LAUNCH(k_newton_step, H->pr, (int)k_outer, (int)l_inner, d_delta, H->d_info);
@@ -1320,7 +1357,10 @@ int alg_newton_solve_async(alg_handle* h, int32_t init, int64_t game_id0) {
     if (!H->x0_set || !H->lqr_set) return fail(ALG_ERR_STATE, "alg_newton_solve: x0 / LQR data not set");
     H->records_bound = 0;                         // newton_solve! starts with reset!(prob.stats)
     if ((rc = reserve_records(H, (long long)H->pr.opt.outer_iter * H->pr.opt.inner_iter + 1))) return rc;
-    return launch_newton_solve(H, (int)init, (uint64_t)game_id0);
+    H->vio_valid = false;
+    if ((rc = launch_newton_solve(H, (int)init, (uint64_t)game_id0))) return rc;
+    H->vio_valid = H->vio_max > 0;                // the solve stores the profiles of its records
+    return ALG_OK;
 }
 int alg_newton_solve(alg_handle* h, int32_t init, int64_t game_id0, alg_game_stats* stats) {
     int rc = alg_newton_solve_async(h, init, game_id0); if (rc) return rc;
@@ -1341,6 +1381,51 @@ int alg_get_history(alg_handle* h, int32_t game, int32_t max_records, alg_record
     int c = std::min(std::min(st.records, p.hist_max), (int)max_records);
     if (c > 0 && (rc = d2h(H, out, p.hist + (size_t)game * p.hist_max, sizeof(alg_record) * c))) return rc;
     if (n_out) *n_out = c;
+    return ALG_OK;
+}
+// Per-record violation profiles of the fused solve (include/algames_hip.h)
+int alg_set_history_profiles(alg_handle* h, int32_t max_records) {
+    NEED_HANDLE("alg_set_history_profiles");
+    if (max_records < 0) return fail(ALG_ERR_ARG, "alg_set_history_profiles: records per game >= 0 (0 = off)");
+    const Params& p = H->pr;
+    if (max_records > 0) {
+        if (!vio_supported(p)) return fail(ALG_ERR_ARG, "alg_set_history_profiles: no solve kernel with violation profiles is compiled for this configuration (seven to ten players have none)");
+        if (H->handoff > 0) return fail(ALG_ERR_ARG, "alg_set_history_profiles: a hand-off budget is set (alg_set_handoff): the hand-off pair stores no profiles");
+        if ((long long)p.B * max_records * (4ll * p.N - 2) * (long long)sizeof(double) > (1ll << 30))
+            return fail(ALG_ERR_ARG, "alg_set_history_profiles: the profile buffer of the batch would exceed 1 GiB (B x max_records x (4 N - 2) doubles)");
+    }
+    if (max_records == H->vio_max) return ALG_OK;
+    int rc = use_device(H); if (rc) return rc;
+    if ((rc = sync(H))) return rc;                // a solve that writes the buffer may still run
+    double* fresh = nullptr;
+    if (max_records > 0 && (rc = dalloc(H, &fresh, (size_t)p.B * (size_t)max_records * (size_t)(4 * p.N - 2), "violation profiles"))) return rc;
+    if (H->d_vio) dfree(H, H->d_vio);
+    H->d_vio = fresh; H->vio_max = max_records; H->vio_valid = false;
+    return sync(H);
+}
+int alg_get_history_profiles(alg_handle* h, int32_t* max_records) {
+    if (!h || !max_records) return fail(ALG_ERR_ARG, "alg_get_history_profiles: null argument");
+    *max_records = H->vio_max; return ALG_OK;
+}
+int alg_get_history_vio(alg_handle* h, int32_t game, int32_t max_records, double* dyn, double* con, double* sta, double* opt, int32_t* n_out) {
+    if (!h || game < 0 || game >= H->pr.B || max_records < 0) return fail(ALG_ERR_ARG, "alg_get_history_vio: bad argument");
+    if (n_out) *n_out = 0;
+    if (H->vio_max == 0 || !H->vio_valid) return ALG_OK;
+    int rc = use_device(H); if (rc) return rc;
+    const Params& p = H->pr;
+    alg_game_stats st;
+    if ((rc = d2h(H, &st, p.arena + (size_t)game * p.stride + p.o_st, sizeof(st)))) return rc;
+    const int c = std::min(std::min(st.records, H->vio_max), (int)max_records), K = p.N - 1;
+    const size_t W = (size_t)(4 * p.N - 2);
+    const double* d = H->d_vio + (size_t)game * H->vio_max * W;
+    auto rows = [&](double* dst, const double* src, int width) -> int {
+        if (!dst || c <= 0) return ALG_OK;
+        HIPCHK(hipMemcpy2DAsync(dst, sizeof(double) * width, src, sizeof(double) * W, sizeof(double) * width, c, hipMemcpyDeviceToHost, H->stream));
+        return ALG_OK;
+    };
+    if ((rc = rows(dyn, d, K)) || (rc = rows(con, d + K, K)) || (rc = rows(sta, d + 2 * K, p.N)) || (rc = rows(opt, d + 2 * K + p.N, p.N))) return rc;
+    if ((rc = sync(H))) return rc;
+    if (n_out) *n_out = std::max(c, 0);
     return ALG_OK;
 }
 // Diagnostic: number of device allocations whose 4 KiB guard zone was overwritten, plus per-game arena chunks (first 64 games)
@@ -1393,6 +1478,7 @@ int alg_ibr_solve_player(alg_handle* h, int32_t player, alg_game_stats* stats) {
     if (player < 0 || player >= H->pr.p) return fail(ALG_ERR_ARG, "alg_ibr_solve_player: bad player index");
     // statistics accumulate over the players' solves (the reference does not reset them between players): room for one more
     if ((rc = reserve_records(H, (long long)H->pr.opt.outer_iter * H->pr.opt.inner_iter + 1))) return rc;
+    H->vio_valid = false;
     IbrOrder order{};
     LAUNCH(k_ibr, H->pr, 0, (int)player, 0, (uint64_t)0, 1, order, 0.0);
     if (stats) return alg_get_stats(h, stats);
@@ -1407,7 +1493,7 @@ int alg_ibr_newton_solve(alg_handle* h, int32_t init, int64_t game_id0, int32_t 
     for (int i = 0; i < H->pr.p; i++) { if (ordering[i] < 0 || ordering[i] >= H->pr.p) return fail(ALG_ERR_ARG, "alg_ibr_newton_solve: ordering entries must be player ids"); order.v[i] = ordering[i]; }
     // records accumulate over rounds and players: ibr_iter * p * (outer_iter * inner_iter + 1) at most -- every record! is kept
     // (reserve_records caps the buffer at ensure_hist's limit; a history beyond it is reported by alg_get_history)
-    H->records_bound = 0;
+    H->records_bound = 0; H->vio_valid = false;
     if ((rc = reserve_records(H, (long long)ibr_iter * H->pr.p * ((long long)H->pr.opt.outer_iter * H->pr.opt.inner_iter + 1)))) return rc;
     LAUNCH(k_ibr, H->pr, 1, 0, (int)init, (uint64_t)game_id0, (int)ibr_iter, order, delta_min);
     if (stats) return alg_get_stats(h, stats);

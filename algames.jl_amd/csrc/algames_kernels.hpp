@@ -20,6 +20,27 @@ __global__ void __launch_bounds__(C::NT, C::WPE) k_newton_solve(Params pr_arg, i
     newton_solve<C>(pr, G, L, init, game_id0 + (uint64_t)g);
 }
 
+// The fused solve that also stores the four .vio vectors of every record (alg_set_history_profiles; vio_profile_phase, algames_solver.hpp;
+// DESIGN.md 3.6).  A sibling of k_newton_solve, not one more argument or a runtime branch of it: k_newton_solve's source, and with it the
+// binary of every solve without profiles, stays what it was.  `vio`: B x vio_max x (4 N - 2) doubles, per record [dyn (N-1) | con (N-1) |
+// sta (N) | opt (N)]; the phase reads the two arguments from the kernel-argument segment (NewtonVioArgs), the by-value copies are unused.
+// Seven to ten players have none: one game per CU, the longest compiles of the library (alg_set_history_profiles refuses them).
+// The siblings are a kernel family of their own, in a namespace of their own (history_vio::k_newton_solve_vio<C>): the k_newton_solve* /
+// k_mpc_loop* families are pinned kernel for kernel against the build before the KKT solves (tests/test_kkt_solve_build.py), these are
+// listed by tests/test_history_vio_abi.py.
+template <class C> inline constexpr bool vio_sibling_v = C::P <= 6;
+namespace history_vio {
+template <class C>
+__global__ void __launch_bounds__(C::NT, C::WPE) k_newton_solve_vio(Params pr_arg, int init, uint64_t game_id0, double* vio_arg, int vio_max_arg) {
+    static_assert(vio_sibling_v<C>, "no profile sibling for seven to ten players");
+    __shared__ Lds<C> L;
+    CPR pr = kernel_params();
+    const int g = blockIdx.x;
+    Game G = game_view(pr, g);
+    newton_solve<C, 0, false, true>(pr, G, L, init, game_id0 + (uint64_t)g);
+}
+} // namespace history_vio
+
 // Straggler hand-off (alg_set_handoff; newton_solve<C, HO>, algames_solver.hpp): the budgeted one-wavefront solve, whose games park after
 // `budget` inner iterations, and the team kernel that resumes the parked games (block b takes the b-th entry of the handle's queue; the
 // launch covers the whole batch, blocks past the queue's count leave at once).
@@ -743,6 +764,16 @@ __global__ void __launch_bounds__(WAVE, C::WPE) k_kkt_solve(Params pr_arg, doubl
 #define ALG_DECLARE_MW(M, P, D, E, W) ALG_INSTANTIATE_MW(extern template, M, P, D, E, W)
 #define ALG_DEFINE_KERNELS(M, P, D, E) ALG_INSTANTIATE_KERNELS(template, M, P, D, E)
 #define ALG_DECLARE_KERNELS(M, P, D, E) ALG_INSTANTIATE_KERNELS(extern template, M, P, D, E)
+// The solves with violation profiles (k_newton_solve_vio): one per solve kernel of the lists above except seven to ten players, in the unit of
+// the solve kernel itself (ALG_DEFINE_KERNELS_VIO / ALG_DEFINE_MW_VIO = the family's kernels plus the sibling; the build's table of families
+// names them for every family that has the sibling).  ALG_VIO_ONE: the one-wavefront configurations that have one, for the host's declarations.
+#define ALG_INSTANTIATE_VIO(PREFIX, M, P, D, E) PREFIX __global__ void history_vio::k_newton_solve_vio<Cfg<M, P, D, E>>(Params, int, uint64_t, double*, int);
+#define ALG_INSTANTIATE_VIO_MW(PREFIX, M, P, D, E, W) PREFIX __global__ void history_vio::k_newton_solve_vio<Cfg<M, P, D, E, W>>(Params, int, uint64_t, double*, int);
+#define ALG_DEFINE_KERNELS_VIO(M, P, D, E) ALG_DEFINE_KERNELS(M, P, D, E) ALG_INSTANTIATE_VIO(template, M, P, D, E)
+#define ALG_DEFINE_MW_VIO(M, P, D, E, W) ALG_DEFINE_MW(M, P, D, E, W) ALG_INSTANTIATE_VIO_MW(template, M, P, D, E, W)
+#define ALG_DECLARE_VIO(M, P, D, E) ALG_INSTANTIATE_VIO(extern template, M, P, D, E)
+#define ALG_DECLARE_VIO_MW(M, P, D, E, W) ALG_INSTANTIATE_VIO_MW(extern template, M, P, D, E, W)
+#define ALG_VIO_ONE(X) ALG_CFGS_BASE(X) ALG_CFGS_BASE_SCEN(X) ALG_CFGS_EXT(X) ALG_CFGS_QUAD(X) ALG_CFGS_QUAD_EXT(X) ALG_CFGS_DI3D(X) ALG_CFGS_P56(X) ALG_CFGS_DI1(X)
 // The scheduled receding-horizon loops (k_mpc_loop_sched): one per loop kernel of the lists above, in units of their own
 #define ALG_INSTANTIATE_SCHED(PREFIX, M, P, D, E) PREFIX __global__ void k_mpc_loop_sched<Cfg<M, P, D, E>>(Params, int, uint64_t, double*, MpcSched, MpcLoopLog, MpcPlant);
 #define ALG_INSTANTIATE_SCHED_MW(PREFIX, M, P, D, E, W) PREFIX __global__ void k_mpc_loop_sched<Cfg<M, P, D, E, W>>(Params, int, uint64_t, double*, MpcSched, MpcLoopLog, MpcPlant);

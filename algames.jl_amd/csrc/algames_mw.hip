@@ -9,6 +9,6 @@
 #if ALG_MW_EXT != 0 && ALG_MW_EXT != 2
 #error "ALG_MW_EXT is the ext column of ALG_CFGS_MW (0) or of ALG_CFGS_MW_SCEN (2)"
 #endif
-ALG_CFGS_MW_E(ALG_DEFINE_MW, ALG_MW_EXT)
+ALG_CFGS_MW_E(ALG_DEFINE_MW_VIO, ALG_MW_EXT)          // (the team kernels and their solves with violation profiles, k_newton_solve_vio)
 // ... and the kernels that resume the games a budgeted one-wavefront solve parked (straggler hand-off, alg_set_handoff)
 ALG_CFGS_HANDOFF_E(ALG_DEFINE_HO_RESUME, ALG_MW_EXT)

@@ -73,6 +73,101 @@ __device__ __forceinline__ RecScalars make_record(CPR pr, const Game& G, Lds<C>&
     return push_stats(pr, G, ro, delta, outer, out);
 }
 
+// Per-record violation profiles (alg_set_history_profiles; no source line of the reference -- its record! pushes whole violation objects, .max and
+// .vio, statistics.jl:44-57 -- DESIGN.md 3.6).  The phase of the sibling kernels k_newton_solve_vio<C> (newton_solve<C, 0, false, VIO = true>)
+// behind every push_stats: the four .vio vectors of the record just pushed -- k_vio_profile's definition (algames_hip.hip), one knot per thread
+// with a stride of the game's C::NT threads -- into slot records - 1 of the game's profile buffer, if that slot exists.
+// Inputs: the rows opt_x | opt_u | dyn of the UNREGULARISED residual are what the record! pass (or the accepted MODE-3 trial that stands in for
+// it) has just left in the step records (Rec::RX / RU / RD): nothing rewrites them between that pass and the Newton direction's refinement, so
+// the per-knot maxima are maxima over the very numbers the record's own maxima were taken over.  The constraint values are evaluated again at
+// pdtraj with dual_penalty_update's expressions (the ones the pass evaluates).  The phase READS the records, pdtraj and the scenario numbers and
+// WRITES its slot: step records, both trajectory buffers, multipliers, constraint values, control slots stay what they were.
+// copy_prev: the final re-push of newton_solve copies the previous record -- its profile is the previous slot's.
+// The buffer pointer and its capacity are the sibling's own kernel arguments behind k_newton_solve's (Params stays what it is for every other
+// kernel); the phase reads them from the kernel-argument segment where it uses them, like k_mpc_loop reads its arguments: nothing of it is
+// live across the solver's phases.  Callable from k_newton_solve_vio only.
+struct NewtonVioArgs { Params pr; int init; uint64_t game_id0; double* vio; int vio_max; };
+template <class C>
+__device__ void vio_profile_phase(CPR pr0, const Game& G0, bool copy_prev) {
+    game_sync();                                     // the pass's records and lane 0's record count
+    CPR pr = phase_params(pr0);
+    const Game G = G0.fresh();
+#if defined(__HIP_DEVICE_COMPILE__)
+    const ALG_AS4 NewtonVioArgs& ka = *(const ALG_AS4 NewtonVioArgs*)uniform_u64((unsigned long long)__builtin_amdgcn_kernarg_segment_ptr());
+#else
+    const NewtonVioArgs& ka = *(const NewtonVioArgs*)nullptr;      // host pass: never executed
+#endif
+    constexpr int n = C::n, m = C::m, P = C::P;
+    using R = Rec<C>;
+    const int N = phase_int(pr.N), K = N - 1, tid = phase_lane(), W = 4 * N - 2;
+    const int cap = ka.vio_max, idx = __builtin_amdgcn_readfirstlane(G.st(pr)->records) - 1;
+    double* const buf = ka.vio;
+    if (buf && idx >= 0 && idx < cap) {
+        double* __restrict__ o = as_global(buf) + ((size_t)G.g * cap + idx) * W;
+        if (copy_prev) {
+            if (idx >= 1) for (int e = tid; e < W; e += C::NT) o[e] = o[e - W];
+        } else {
+            const double* __restrict__ z = G.z(0); const double* __restrict__ recs = G.rec(pr);
+            auto pos = [](double c) { return (isfinite(c) && c > 0.0) ? c : 0.0; };
+            for (int j = tid; j < N; j += C::NT) {
+                double vopt = 0.0, vsta = 0.0;
+                if (j < K) {
+                    const double* rj = recs + (size_t)j * R::LEN;
+                    double vdyn = 0.0, vcon = 0.0;
+                    for (int a = 0; a < n; a++) vdyn = fmax(vdyn, fabs(rj[R::RD + a]));
+                    for (int c = 0; c < m; c++) vopt = fmax(vopt, fabs(rj[R::RU + c]));                      // opt_i,u_{i,k}, knot j + 1
+                    if (pr.has_ctl) {
+                        for (int c = 0; c < m; c++) {
+                            const double u = z[n + hu<C>(j, 0) + uoff<C>(c)];
+                            vcon = fmax(vcon, pos(u - ALG_SCEN_AT(C, pr, G, umax, SC_UMAX, c)));
+                            vcon = fmax(vcon, pos(ALG_SCEN_AT(C, pr, G, umin, SC_UMIN, c) - u));
+                        }
+                    }
+                    o[j] = vdyn; o[K + j] = vcon;
+                }
+                if (j >= 1) {
+                    const int k = j - 1;                                                                     // step whose x_{k+1} is knot j + 1
+                    const double* rk = recs + (size_t)k * R::LEN;
+                    for (int e = 0; e < P * n; e++) vopt = fmax(vopt, fabs(rk[R::RX + e]));                  // opt_i,x, knot j + 1
+                    const double* x = zstate<C>(z, j);
+                    if constexpr (P > 1) {
+                        if (pr.has_colavoid) {
+                            for (int i = 0; i < P; i++)
+                                for (int jj = 0; jj < P - 1; jj++) {
+                                    const int q = jj < i ? jj : jj + 1;
+                                    const double d0 = x[i] - x[q], d1 = x[P + i] - x[P + q], Rr = ALG_SCEN_AT(C, pr, G, ca_pair_r, SC_CAR, i * MAXP + q);
+                                    double s2 = pair_dist2(d0, d1);
+                                    if constexpr (C::PD == 3) { const double d2 = pr.ca_dim == 3 ? x[2 * P + i] - x[2 * P + q] : 0.0; s2 = __builtin_fma(d2, d2, s2); }
+                                    vsta = fmax(vsta, pos(ca_value((double)((pr.ca_mask[i] >> q) & 1u), Rr, s2)));
+                                }
+                        }
+                    }
+                    if constexpr (C::EXT) {
+                        const double* ec = scen_ext(pr, G);
+                        for (int i = 0; i < P; i++) {
+                            if (pr.sb_len)
+                                for (int a = 0; a < n; a++) {
+                                    vsta = fmax(vsta, pos(x[a] - ext_sbmax(pr, ec)[i * n + a]));
+                                    vsta = fmax(vsta, pos(ext_sbmin(pr, ec)[i * n + a] - x[a]));
+                                }
+                            double gx, gy;
+                            for (int w = 0; w < pr.nwall; w++) vsta = fmax(vsta, pos((double)((pr.wall_mask[i] >> w) & 1u) * wall_val(ext_walls(pr, ec), w, x[i], x[P + i], &gx, &gy)));
+                            for (int w = 0; w < pr.ncirc; w++) vsta = fmax(vsta, pos((double)((pr.circ_mask[i] >> w) & 1u) * circ_val(ext_circs(pr, ec), w, x[i], x[P + i], &gx, &gy)));
+                            if constexpr (C::PD == 3) {
+                                const double q3[3] = {x[i], x[P + i], x[2 * P + i]}; double g[3];
+                                for (int w = 0; w < pr.nwall3; w++) vsta = fmax(vsta, pos((double)((pr.wall3_mask[i] >> w) & 1u) * wall3_val(ext_walls3(pr, ec), w, q3, g)));
+                                for (int w = 0; w < pr.ncyl; w++) vsta = fmax(vsta, pos((double)((pr.cyl_mask[i] >> w) & 1u) * cyl_val(ext_cyls(pr, ec), w, q3, g)));
+                            }
+                        }
+                    }
+                }
+                o[2 * K + j] = vsta; o[2 * K + N + j] = vopt;
+            }
+        }
+    }
+    game_sync();                                     // a team's other wavefronts still read the records the direction is about to rewrite
+}
+
 // line_search (solver_methods.jl:105-125).  jreg_next >= 0: every trial also leaves the unregularised statistics and
 // step records (R^ with jreg_next) so that an accepted trial can serve as the next iteration's record!.
 template <class C>
@@ -164,7 +259,8 @@ template <class C> __device__ __forceinline__ void rotate_priority(int it) {
 }
 // inner_iteration (solver_methods.jl:67-103).  Returns status (bits 0-7) | control_flow << 8; step details go to
 // the history record / *info (lane 0).  `cache` (optional) carries an accepted trial's statistics to the next call.
-template <class C>
+// VIO (k_newton_solve_vio only): every record! is followed by the profile phase (vio_profile_phase)
+template <class C, bool VIO = false>
 __device__ __forceinline__ int inner_iteration(CPR pr0, Game& G_, Lds<C>& L, int& LS_count, double& Delta, int k, int l,
                                alg_step_info* info, int* cache_valid) {
     Game& G = G_;
@@ -181,6 +277,7 @@ __device__ __forceinline__ int inner_iteration(CPR pr0, Game& G_, Lds<C>& L, int
     // iteration is still due and rides on this record! pass (fused kernels)
     if (cache_valid && *cache_valid == 1) { ResOut cro; tcache_load(pr, G, cro); rs = push_stats(pr, G, cro, Delta, k, info ? &info->rec : nullptr); }
     else rs = make_record<C>(pr, G, L, Delta, k, reg, info ? &info->rec : nullptr, AsmLds<C>::FUSED && cache_valid && *cache_valid == 2);
+    if constexpr (VIO) vio_profile_phase<C>(pr, G, false);
     if (cache_valid) *cache_valid = 0;
     Delta = 0.0;                                                           // :79
     auto finish = [&](int status, int flow) { if (info && lane0) { info->status = status; info->control_flow = flow; } iter_clock_stop(pr, G_); return status | (flow << 8); };
@@ -486,8 +583,9 @@ __device__ __forceinline__ void handoff_park(CPR pr0, Game& G, int k, int l, int
 }
 
 // newton_solve! (solver_methods.jl:5-65)
-template <class C, int HO = 0, bool LOOP = false>
+template <class C, int HO = 0, bool LOOP = false, bool VIO = false>
 __device__ __forceinline__ void newton_solve(CPR pr, Game& G, Lds<C>& L, int init, uint64_t game_id, int shift = -1, int dual_reset = -1, int budget = 0) {
+    static_assert(!VIO || (HO == 0 && !LOOP), "profiles: the plain fused solve only (no hand-off pair, no receding-horizon loop)");
     const auto& o = pr.opt; const int lane = phase_lane();
     int k0 = 1, l0 = 1, ls0 = 0, cv0 = 0; double Delta = 0.0;
 #ifdef ALG_PHASE_PROF
@@ -548,7 +646,7 @@ __device__ __forceinline__ void newton_solve(CPR pr, Game& G, Lds<C>& L, int ini
                 if (started >= budget) { handoff_park<C>(pr, G, k, l, LS_count, cache_valid, Delta); return; }
                 started += 1;
             }
-            const int rcode = inner_iteration<C>(pr, G, L, LS_count, Delta, k, l, nullptr, &cache_valid);
+            const int rcode = inner_iteration<C, VIO>(pr, G, L, LS_count, Delta, k, l, nullptr, &cache_valid);
             fresh = (rcode >> 16) & 1;
             if ((rcode & 0xff) != ALG_STATUS_OK) { status = rcode & 0xff; break; }
             if (LS_count >= 1 || ((rcode >> 8) & 0xff) == 1) break;        // :43
@@ -588,7 +686,11 @@ __device__ __forceinline__ void newton_solve(CPR pr, Game& G, Lds<C>& L, int ini
             }
             st->records = idx + 1;
         }
-    } else make_record<C>(pr, G, L, Delta, out, 0.0, nullptr);
+        if constexpr (VIO) vio_profile_phase<C>(pr, G, true);
+    } else {
+        make_record<C>(pr, G, L, Delta, out, 0.0, nullptr);
+        if constexpr (VIO) vio_profile_phase<C>(pr, G, false);
+    }
     settle_traj<C>(pr, G);
     if (phase_lane() == 0) { alg_game_stats* st = G.fresh().st(phase_params(pr)); st->status = status; st->outer_iters = out; }
 #ifdef ALG_PHASE_PROF

@@ -497,14 +497,21 @@ class Statistics:
     """Per-game `Statistics` history (src/struct/statistics.jl:5-15) as numpy record arrays; the reference's field names
     (`outer_iter`, `res`, `Δ_traj`, `dyn_vio`, `con_vio`, `sta_vio`, `opt_vio`) are views of game 0's history, the `*_vio`
     entries being the `.max` of the reference's violation objects.  `t_elap[r]` is the duration (seconds) of the inner iteration
-    that preceded record r, measured on the device with the 100 MHz real-time counter (0 for the first record of a solve)."""
+    that preceded record r, measured on the device with the 100 MHz real-time counter (0 for the first record of a solve).
+    `vio(game)` are the `.vio` vectors of the same records when the solve ran with history profiles on (`history_profiles=`)."""
 
-    def __init__(self, summary, history_fn):
+    def __init__(self, summary, history_fn, vio_fn=None):
         self.summary = summary
         self._history_fn = history_fn
+        self._vio_fn = vio_fn
 
     def history(self, game=0):
         return self._history_fn(game)
+
+    def vio(self, game=0):
+        """dict(dyn, con, sta, opt) of shape (records, N-1 | N): the per-knot profiles of every stored record of `game`, row r next to
+        record r of history(game); None when the solve ran with history profiles off."""
+        return None if self._vio_fn is None else self._vio_fn(game)
 
     @property
     def iter(self):
@@ -757,8 +764,11 @@ def _obj_row(game_obj, g):
 
 
 class GameProblem:
-    def __init__(self, N, dt, x0, model, opts, game_obj, game_con, backend=None, device=0, game_id0=0, scenario_kernels="ext"):
-        """scenario_kernels: "ext" (default) or "base" -- which kernels per-game data of the base kinds runs on
+    def __init__(self, N, dt, x0, model, opts, game_obj, game_con, backend=None, device=0, game_id0=0, scenario_kernels="ext",
+                 history_profiles=0):
+        """history_profiles: records per game whose `.vio` vectors newton_solve stores next to the history (Statistics.vio; 0 = off,
+        the default; Batch.set_history_profiles -- the CPU oracle has no such entry point and raises AlgamesError).
+        scenario_kernels: "ext" (default) or "base" -- which kernels per-game data of the base kinds runs on
         (Batch.set_scenario_kernels).  With "base" a problem that carries only the base constraint set keeps the base kernels (fused
         pass, teams, hand-off); every base kind the problem carries is still uploaded, so every shard takes the whole batch's path."""
         if scenario_kernels not in ("ext", "base"):
@@ -839,6 +849,12 @@ class GameProblem:
         for gc in (self.game_cons or [game_con]):
             gc.active_set_tolerance = opts.active_set_tolerance        # set_constraint_params!, game_constraints.jl:37
         self._sync_options()       # set_constraint_params!(game_con, opts), problem.jl:49
+        if history_profiles:
+            self.set_history_profiles(history_profiles)
+
+    def set_history_profiles(self, max_records):
+        """Per-record violation profiles of newton_solve (Batch.set_history_profiles): capacity in records per game, 0 = off."""
+        self.batch.set_history_profiles(max_records)
 
     def _sync_options(self):
         # `opts` is shared by reference in Julia and read at solve time (tests mutate it after construction)
@@ -919,10 +935,14 @@ def _init_traj_host_fill(o, X, U, L, B, N, n, m, p, s, draw):
                 L[g, i, k - 1] = L[g, i, k + s - 1] if k + s <= N - 1 else draw(n)
 
 
-def newton_solve(prob, init=True):
+def newton_solve(prob, init=True, history_profiles=None):
     """newton_solve!(prob) for every game of the batch (solver_methods.jl:5-65).
     init=False keeps the stored controls/duals as the initial guess (explicit warm start).
+    history_profiles: None keeps the problem's setting; a count sets it first (prob.set_history_profiles; 0 = off) -- with profiles on,
+    prob.stats.vio(game) returns the `.vio` vectors of every stored record.
     A `sharding.ShardedGameProblem` (batch split over several devices) is solved on all of its devices concurrently."""
+    if history_profiles is not None:
+        prob.set_history_profiles(history_profiles)
     if hasattr(prob, "shards"):
         from . import sharding
         if init and any(callable(q.opts.f_init) for q in prob.shards):
@@ -935,7 +955,7 @@ def newton_solve(prob, init=True):
         init_traj_host(prob)
         init = False
     summary = prob.batch.newton_solve(init=init, game_id0=prob.game_id0)
-    prob.stats = Statistics(summary, prob.batch.get_history)
+    prob.stats = Statistics(summary, prob.batch.get_history, prob.batch.get_history_vio if prob.batch.get_history_profiles() > 0 else None)
     if prob.opts.inner_print:
         _print_history(prob)
     return None

@@ -419,7 +419,10 @@ function pull_results!(bp::BatchedGameProblem, stats::Vector{AlgGameStats})
         end
     end
     # prob.stats: one record! per stored record (statistics.jl:30-57); the violation objects carry the recorded maxima (what the
-    # solver's exit test and the plot recipes read, solver_plots.jl:83-125); the final record also gets its per-knot profiles
+    # solver's exit test and the plot recipes read, solver_plots.jl:83-125); the final record also gets its per-knot profiles --
+    # with history profiles on (set_history_profiles!) EVERY stored record gets the .vio vectors the solve stored next to it
+    pcap = Ref{Int32}(0)
+    check(ccall((:alg_get_history_profiles, LIB), Cint, (Ptr{Cvoid}, Ref{Int32}), bp.h, pcap))
     cap = max(Int(maximum(s.records for s in stats)), 1)
     rec = Vector{AlgRecord}(undef, cap); cnt = Ref{Int32}(0)
     # the .vio vectors of the four violation objects at the final iterate (violations.jl), all games in one call
@@ -437,7 +440,17 @@ function pull_results!(bp::BatchedGameProblem, stats::Vector{AlgGameStats})
             ov = Algames.OptimalityViolation(N); ov.max = r.opt_vio
             Algames.record!(pr.stats, r.t_elap, r.res, r.delta, dv, cvv, sv, ov, Int(r.outer))      # t_elap: device real-time counter
         end
-        if cnt[] > 0                                                # final record (solver_methods.jl:63): per-knot profiles from the device
+        nvio = Ref{Int32}(0)
+        if pcap[] > 0 && cnt[] > 0                                  # row-major n x (N-1 | N) of the ABI = column t of these matrices is record t
+            hdyn = zeros(N - 1, cnt[]); hcon = zeros(N - 1, cnt[]); hsta = zeros(N, cnt[]); hopt = zeros(N, cnt[])
+            check(ccall((:alg_get_history_vio, LIB), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int32}),
+                        bp.h, g - 1, cnt[], hdyn, hcon, hsta, hopt, nvio))
+            for t in 1:nvio[]
+                pr.stats.dyn_vio[t].vio .= view(hdyn, :, t); pr.stats.con_vio[t].vio .= view(hcon, :, t)
+                pr.stats.sta_vio[t].vio .= view(hsta, :, t); pr.stats.opt_vio[t].vio .= view(hopt, :, t)
+            end
+        end
+        if cnt[] > 0 && nvio[] < cnt[]                              # final record (solver_methods.jl:63): per-knot profiles from the device
             pr.stats.dyn_vio[end].vio .= view(vdyn, :, g); pr.stats.con_vio[end].vio .= view(vcon, :, g)
             pr.stats.sta_vio[end].vio .= view(vsta, :, g); pr.stats.opt_vio[end].vio .= view(vopt, :, g)
         end
@@ -692,6 +705,14 @@ park and a second launch finishes them with the team kernel; `0` switches it off
 number of games the most recent solve handed over.
 """
 set_handoff!(bp::BatchedGameProblem, iters::Integer) = check(ccall((:alg_set_handoff, LIB), Cint, (Ptr{Cvoid}, Int32), bp.h, iters))
+"""
+    set_history_profiles!(bp, max_records)
+
+Per-record violation profiles (alg_set_history_profiles): with `max_records > 0` `newton_solve!` stores the `.vio` vectors of every record it pushes,
+up to `max_records` records per game, and `pull_results!` fills `.vio` of every stored record of `prob.stats` from them; `0` switches it off (the
+default: only the final record carries its profiles).  Refused for seven to ten players and while a hand-off budget is set.
+"""
+set_history_profiles!(bp::BatchedGameProblem, max_records::Integer) = check(ccall((:alg_set_history_profiles, LIB), Cint, (Ptr{Cvoid}, Int32), bp.h, max_records))
 function handoff(bp::BatchedGameProblem)
     k = Ref{Int32}(0); n = Ref{Int32}(0)
     check(ccall((:alg_get_handoff, LIB), Cint, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}), bp.h, k, n))

@@ -21,7 +21,8 @@ class ShardedGameProblem:
     does not change them).  A per-game LQR block (arrays with a leading batch axis) is split with the batch.  All shards run the
     same kernel shape: `waves_per_game`, default = what the first shard's batch size selects automatically."""
 
-    def __init__(self, N, dt, x0, model, opts, game_obj, game_con, devices=(0,), backend=None, game_id0=0, waves_per_game=None, scenario_kernels="ext"):
+    def __init__(self, N, dt, x0, model, opts, game_obj, game_con, devices=(0,), backend=None, game_id0=0, waves_per_game=None, scenario_kernels="ext",
+                 history_profiles=0):
         x0 = np.ascontiguousarray(np.asarray(x0, dtype=np.float64).reshape(-1, model.n))
         self.B, self.devices = x0.shape[0], list(devices)
         if not self.devices:
@@ -40,12 +41,24 @@ class ShardedGameProblem:
         self.waves_per_game = int(waves_per_game) if waves_per_game is not None else int(self.shards[0].batch.get_waves_per_game())
         for s in self.shards:
             s.batch.set_waves_per_game(self.waves_per_game)
+        if history_profiles:
+            self.set_history_profiles(history_profiles)
         self.stats = None
 
     # ---- the pieces of the GameProblem surface that make sense on a sharded batch
     def _sync_options(self):
         for s in self.shards:
             s._sync_options()
+
+    def set_history_profiles(self, max_records):
+        """Per-record violation profiles (GameProblem.set_history_profiles) on every shard's handle: one capacity for all of them."""
+        for s in self.shards:
+            s.set_history_profiles(max_records)
+
+    def history_vio(self, game, **kw):
+        """Batch.get_history_vio of the shard that owns `game` (the sibling of the history closure of newton_solve_sharded)"""
+        s, g = self.locate(game)
+        return s.batch.get_history_vio(g, **kw)
 
     def get_traj(self, which=0):
         return np.concatenate([s.batch.get_traj(which) for s in self.shards])
@@ -100,9 +113,10 @@ def newton_solve_sharded(prob, init=True):
     def history(game, **kw):
         s, g = prob.locate(game)
         return s.batch.get_history(g, **kw)
-    prob.stats = host.Statistics(summary, history)
+    on = all(s.batch.get_history_profiles() > 0 for s in prob.shards)
+    prob.stats = host.Statistics(summary, history, prob.history_vio if on else None)
     for s, (lo, hi) in zip(prob.shards, prob.cuts):
-        s.stats = host.Statistics(summary[lo:hi], s.batch.get_history)
+        s.stats = host.Statistics(summary[lo:hi], s.batch.get_history, s.batch.get_history_vio if on else None)
     return None
 
 

@@ -429,6 +429,24 @@ int alg_get_stats(alg_handle* h, alg_game_stats* stats /*B*/);
  * past the capacity are dropped, .last is always the final record) -- callers must treat n_out < records as truncation. */
 #define ALG_HIST_MAX 192
 int alg_get_history(alg_handle* h, int32_t game, int32_t max_records, alg_record* out, int32_t* n_out);
+/* Per-record violation profiles: the .vio vectors the reference's record! pushes next to every .max (statistics.jl:44-57,
+ * violations.jl:5-26, 41-67, 86-114, 140-168).  With max_records > 0 alg_newton_solve / alg_newton_solve_async also store, for every
+ * record they push, the four vectors of alg_get_violation_profile at the iterate of that record: (N-1) + (N-1) + N + N doubles in that
+ * call's layout (dyn, con: steps 1..N-1; sta, opt: knots 1..N, sta[0] = 0).  The buffer is an allocation of its own, B x max_records x
+ * (4 N - 2) doubles; alg_record and the history buffer do not change.  Record r of a game goes to slot r while r < max_records; later
+ * records are dropped, exactly as the history drops records past its capacity.  0 (default) = off: the buffer is freed and the solve runs
+ * the kernels it always ran (with profiles on it runs their siblings, which add one phase behind every record!; results are bit-identical).
+ * alg_set_history_profiles returns ALG_ERR_ARG, with a message and nothing changed, for a negative count, for a buffer beyond 1 GiB for
+ * the batch, for a configuration without a sibling kernel (seven to ten players), and while a hand-off budget is set; alg_set_handoff(h,
+ * K > 0) is refused in turn while profiles are on.
+ * alg_get_history_vio: the profiles of one game.  dyn, con: n x (N-1); sta, opt: n x N, row-major, row r = record r of alg_get_history;
+ * any pointer may be NULL; *n_out = n = min(records, capacity, max_records).  The profiles belong to the most recent alg_newton_solve /
+ * alg_newton_solve_async: these two write them, every other entry point that pushes records (alg_newton_step, alg_record_stats,
+ * alg_ibr_solve_player, alg_ibr_newton_solve, alg_mpc_solve, alg_mpc_solve_log) invalidates them -- *n_out = 0 until the next solve --
+ * and alg_kkt_solve leaves them alone, as it leaves the history alone.  With profiles off: ALG_OK and *n_out = 0. */
+int alg_set_history_profiles(alg_handle* h, int32_t max_records);
+int alg_get_history_profiles(alg_handle* h, int32_t* max_records);
+int alg_get_history_vio(alg_handle* h, int32_t game, int32_t max_records, double* dyn, double* con, double* sta, double* opt, int32_t* n_out);
 int alg_synchronize(alg_handle* h);
 /* Diagnostic (tests): every device allocation is followed by a 4 KiB guard zone and the per-game segments of the arenas are
  * padded to 128-byte lines; returns the number of guard zones / paddings a kernel has written to (0 = clean, <0 = error). */
