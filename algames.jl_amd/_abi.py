@@ -169,12 +169,17 @@ SIGNATURES = {
     "mpc_set_plant": (C.c_int, [_P, C.POINTER(alg_mpc_plant)]),
     "mpc_get_plant": (C.c_int, [_P, C.POINTER(alg_mpc_plant)]),
     "mpc_plant_advance": (C.c_int, [_P, C.c_int32]),
+    "get_cost": (C.c_int, [_P, C.c_int32, _D, _D]),
+    "mpc_set_cost_log": (C.c_int, [_P, C.c_int32]),
+    "mpc_get_cost_log": (C.c_int, [_P, _I]),
+    "mpc_get_cost": (C.c_int, [_P, C.c_int32, _D, _D, _I]),
 }
 # Entry points a backend may lack (the CPU oracle has no per-game scenario data): bound when present; calling one that is absent
 # raises AlgamesError naming the backend.
 OPTIONAL = frozenset({"scenario_data_len", "set_scenario_data", "get_scenario_data", "set_scenario_kernels", "get_scenario_kernels",
                       "mpc_set_schedule", "mpc_get_schedule", "mpc_solve_log", "mpc_set_plant", "mpc_get_plant", "mpc_plant_advance", "kkt_solve",
-                      "set_history_profiles", "get_history_profiles", "get_history_vio"})
+                      "set_history_profiles", "get_history_profiles", "get_history_vio",
+                      "get_cost", "mpc_set_cost_log", "mpc_get_cost_log", "mpc_get_cost"})
 
 
 class AlgamesError(RuntimeError):
@@ -575,6 +580,18 @@ class Batch:
         self.lib.check(self.lib.get_violation_profile(self.h, _dptr(out["dyn"]), _dptr(out["con"]), _dptr(out["sta"]), _dptr(out["opt"])))
         return out
 
+    def get_cost(self, which=ALG_TRAJ_PD, stage=False):
+        """What the plan costs each player (alg_get_cost): total (B, p, 3) with the components [state, control, collision] of
+        J_i = sum_k w_k l_i(x_k, u_k), w_k = dt for k < N and w_N = 1 -- the objective, without constraints, multipliers or penalties.
+        which: ALG_TRAJ_PD or ALG_TRAJ_TRIAL.  stage=True returns (total, stage (B, N, p, 3)), the summands w_k l_i per knot.
+        Changes nothing on the handle; a backend without the entry point (the CPU oracle) raises AlgamesError."""
+        if isinstance(which, bool) or not isinstance(which, (int, np.integer)) or int(which) not in (ALG_TRAJ_PD, ALG_TRAJ_TRIAL):
+            raise ValueError(f"get_cost: which must be ALG_TRAJ_PD (0) or ALG_TRAJ_TRIAL (1), got {which!r}")
+        total = np.empty((self.B, self.p, 3))
+        st = np.empty((self.B, self.N, self.p, 3)) if stage else None
+        self.lib.check(self.lib.get_cost(self.h, int(which), _dptr(total), _dptr(st)))
+        return (total, st) if stage else total
+
     def newton_direction(self, reg=0.0):
         delta = np.empty((self.B, self.S)); st = np.empty(self.B, dtype=np.int32)
         self.lib.check(self.lib.newton_direction(self.h, reg, _dptr(delta), _iptr(st)))
@@ -755,6 +772,34 @@ class Batch:
         gs = np.zeros((steps, self.B), dtype=game_stats_dtype) if stats else None
         self.lib.check(self.lib.mpc_solve_log(self.h, steps, int(game_id0), _dptr(st), _dptr(uc), None if gs is None else gs.ctypes.data_as(_P)))
         return st, uc, gs
+
+    def mpc_set_cost_log(self, on=True):
+        """Closed-loop cost log of mpc_solve / mpc_solve_log (alg_mpc_set_cost_log; off by default): with it on the loop also leaves the
+        running cost of every plant knot and player on the device (mpc_get_cost).  A backend without it (the CPU oracle) raises AlgamesError."""
+        if not isinstance(on, (bool, int, np.integer)):
+            raise ValueError(f"mpc_set_cost_log: on must be a bool, got {on!r}")
+        self.lib.check(self.lib.mpc_set_cost_log(self.h, int(bool(on))))
+
+    def mpc_get_cost_log(self):
+        v = C.c_int32()
+        self.lib.check(self.lib.mpc_get_cost_log(self.h, C.byref(v)))
+        return bool(v.value)
+
+    def mpc_get_cost(self, max_knots=None):
+        """The cost log of the most recent mpc_solve / mpc_solve_log (alg_mpc_get_cost; waits for the stream): (stage (k, B, p, 3), total
+        (B, p, 3)) -- stage[q, g, i] = dt l_i(states[q], controls[q]) in the components [state, control, collision] with the schedule rows
+        the knot's solve used, total their sum over ALL knots of the run, k = min(max_knots, knots).  (None, None) while there is none:
+        log off, no loop yet, or invalidated by an adder, set_lqr, set_scenario_data or mpc_set_schedule."""
+        if max_knots is not None and (isinstance(max_knots, bool) or not isinstance(max_knots, (int, np.integer)) or max_knots < 0):
+            raise ValueError(f"mpc_get_cost: max_knots must be a non-negative integer or None, got {max_knots!r}")
+        v = C.c_int32()
+        self.lib.check(self.lib.mpc_get_cost(self.h, 0, None, None, C.byref(v)))
+        if v.value == 0:
+            return None, None
+        k = v.value if max_knots is None else min(int(max_knots), v.value)
+        stage = np.empty((k, self.B, self.p, 3)); total = np.empty((self.B, self.p, 3))
+        self.lib.check(self.lib.mpc_get_cost(self.h, k, _dptr(stage), _dptr(total), C.byref(v)))
+        return stage, total
 
     # ---- schedules of the fused loop (alg_mpc_set_schedule) ----------------------------------
     def _sched_kind(self, kind):

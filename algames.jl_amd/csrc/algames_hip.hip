@@ -258,6 +258,11 @@ struct Handle {
     Sched dist;                   // the plant disturbance (ALG_SCHED_DISTURBANCE): rows x B x n, no block offsets; rows = 0: none
     MpcPlant plant{1, 1, ALG_PLANT_RK2, 0};   // alg_mpc_set_plant: independent of constraints and LQR data, nothing but the call itself changes it
     bool keep_sched = false;      // set while alg_set_scenario_data's own switch to the EXT kernels runs (it is no adder: schedules stay)
+    // closed-loop cost log of the fused loop (alg_mpc_set_cost_log): [stage (knots x B x p x 3) | total (B x p x 3)], an allocation of its own
+    bool cost_log = false;
+    double* d_cost = nullptr;
+    size_t cost_cap = 0;          // plant knots the buffer holds
+    int cost_knots = 0;           // plant knots of the loop the buffer belongs to; 0 = none / invalidated (adders, alg_set_lqr, alg_set_scenario_data, alg_mpc_set_schedule)
 };
 
 constexpr size_t GUARD = 4096;     // guard zone behind every device buffer (checked by alg_debug_check_guards)
@@ -531,6 +536,7 @@ void scen_image(const Handle* hd, double* blk) {
 int scen_commit(Handle* hd) {
     Params& p = hd->pr;
     if (!hd->keep_sched) sched_drop_all(hd);       // an adder drops every schedule, as it drops per-game data
+    hd->cost_knots = 0;                            // ... and the cost log no longer belongs to the handle's data
     hd->scen_kinds = 0;
     p.scen = hd->d_scen; p.scen_stride = 0;
     if (p.ext == 2) p.ext = 0;
@@ -735,6 +741,7 @@ int set_scenario_data(alg_handle* h, const char* who, int32_t kind, const double
     scen_image(H, img.data());
     int rc = use_device(H); if (rc) return rc;
     if (!data) {                  // back to the shared values
+        H->cost_knots = 0;
         if (!((H->scen_kinds >> kind) & 1u)) return ALG_OK;
         H->scen_kinds &= ~(1u << kind);
         if (!H->scen_kinds) { p.scen = H->d_scen; p.scen_stride = 0; if (p.ext == 2) p.ext = 0; return ALG_OK; }
@@ -766,6 +773,7 @@ int set_scenario_data(alg_handle* h, const char* who, int32_t kind, const double
     H->scen_kinds |= 1u << kind;
     p.scen = H->d_scen_games; p.scen_stride = (int)SS;
     if (stay_base) p.ext = 2;
+    H->cost_knots = 0;
     return ALG_OK;
 }
 
@@ -780,20 +788,48 @@ int mpc_solve_impl(const char* who, alg_handle* h, int32_t steps, int64_t game_i
     // states and controls hold one row per plant knot, steps x hold of them
     const size_t knots = (size_t)steps * (size_t)H->plant.hold;
     const bool planted = !mpc_plant_is_default(H->plant.hold, H->plant.substeps, H->plant.integrator);
-    const size_t b_st = states ? sizeof(double) * (knots + 1) * p.B * p.n : 0, b_uc = controls ? sizeof(double) * knots * p.B * p.m : 0,
+    // the cost log (alg_mpc_set_cost_log) is evaluated from the device-resident state and control logs: they are kept in the scratch whether
+    // or not the caller asks for them
+    const bool clog = H->cost_log;
+    H->cost_knots = 0;
+    if (clog) {
+        const size_t per = (size_t)p.B * p.p * 3;
+        if (knots + 1 > ((size_t)1 << 30) / (sizeof(double) * per)) return fail(ALG_ERR_ARG, std::string(who) + ": the cost log of this run would exceed 1 GiB");
+        if (knots > H->cost_cap) {
+            if ((rc = sync(H))) return rc;
+            if (H->d_cost) dfree(H, H->d_cost);
+            H->d_cost = nullptr; H->cost_cap = 0;
+            if ((rc = dalloc(H, &H->d_cost, (knots + 1) * per, "closed-loop cost log"))) return rc;
+            H->cost_cap = knots;
+        }
+    }
+    const size_t b_st = (states || clog) ? sizeof(double) * (knots + 1) * p.B * p.n : 0, b_uc = (controls || clog) ? sizeof(double) * knots * p.B * p.m : 0,
                  b_gs = stats ? sizeof(alg_game_stats) * (size_t)steps * p.B : 0;
     static_assert(sizeof(alg_game_stats) % 8 == 0, "the stats log follows doubles in the scratch");
     if (b_st + b_uc + b_gs && (rc = ensure_scratch(H, b_st + b_uc + b_gs))) return rc;
     char* const d0 = (char*)H->d_scratch;
-    double* const d_states = states ? (double*)d0 : nullptr;
-    double* const d_controls = controls ? (double*)(d0 + b_st) : nullptr;
+    double* const d_states = b_st ? (double*)d0 : nullptr;
+    double* const d_controls = b_uc ? (double*)(d0 + b_st) : nullptr;
     alg_game_stats* const d_stats = stats ? (alg_game_stats*)(d0 + b_st + b_uc) : nullptr;
     bool scheduled = false;
     for (int k = 0; k < ALG_SCHED_MAX_KINDS; k++) scheduled |= H->sched[k].rows > 0;
     // the sibling kernels are the loop with per-step phases: a schedule, a disturbance, a log or a plant takes them
-    if (!scheduled && !H->dist.rows && !controls && !stats && !planted) rc = launch_mpc_loop(H, (int)steps, (uint64_t)game_id0, d_states);
+    if (!scheduled && !H->dist.rows && !controls && !stats && !planted && !clog) rc = launch_mpc_loop(H, (int)steps, (uint64_t)game_id0, d_states);
     else rc = launch_mpc_loop_sched(H, (int)steps, (uint64_t)game_id0, d_states, d_controls, d_stats);
     if (rc) return rc;
+    if (clog) {
+        // behind the loop on the same stream: [stage | total] of the handle's own buffer, rows of the schedules the loop read
+        CostLoopArgs ca; std::memset(&ca, 0, sizeof(ca));
+        ca.states = d_states; ca.controls = d_controls;
+        ca.stage = H->d_cost; ca.total = H->d_cost + knots * (size_t)p.B * p.p * 3;
+        ca.knots = (int)knots; ca.hold = H->plant.hold;
+        const Handle::Sched& tg = H->sched[sched_slot(ALG_SCHED_LQR_TARGET)];
+        if (tg.rows) { ca.tgt = tg.d_data; ca.tgt_rows = tg.rows; }
+        const Handle::Sched& cc = H->sched[sched_slot(ALG_SCEN_COLLISION_COST)];
+        if (cc.rows) { ca.cc = cc.d_data; ca.cc_rows = cc.rows; }
+        LAUNCH(k_closed_loop_cost, H->pr, ca);
+        H->cost_knots = (int)knots;
+    }
     // the loop leaves the row its last step used in the games' blocks: the host mirror of the scenario blocks follows (what the step-wise
     // alg_set_scenario_data calls would have left; the LQR blocks have no host mirror)
     for (int k = 0; scheduled && k < ALG_SCHED_MAX_KINDS - 1; k++) {
@@ -814,7 +850,7 @@ int mpc_solve_impl(const char* who, alg_handle* h, int32_t steps, int64_t game_i
 // The plant disturbance (ALG_SCHED_DISTURBANCE): rows x B x n, needs nothing of the handle but its sizes
 int set_disturbance(Handle* hd, int32_t rows, const double* data) {
     int rc = use_device(hd); if (rc) return rc;
-    if (!data) { sched_drop(hd, hd->dist); return ALG_OK; }
+    if (!data) { sched_drop(hd, hd->dist); hd->cost_knots = 0; return ALG_OK; }
     if (rows < 1) return fail(ALG_ERR_ARG, "alg_mpc_set_schedule: rows must be >= 1");
     const Params& p = hd->pr;
     const size_t per_row = (size_t)p.B * p.n, cnt = (size_t)rows * per_row;
@@ -826,6 +862,7 @@ int set_disturbance(Handle* hd, int32_t rows, const double* data) {
     if ((rc = h2d(hd, sc.d_data, data, sizeof(double) * cnt))) { dfree(hd, sc.d_data); return rc; }
     sched_drop(hd, hd->dist);
     hd->dist = std::move(sc);
+    hd->cost_knots = 0;
     return ALG_OK;
 }
 
@@ -981,6 +1018,7 @@ int alg_set_lqr(alg_handle* h, const double* Qd, const double* Rd, const double*
     if ((rc = sync(H))) return rc;
     p.lqr_per_game = per_game ? 1 : 0; p.lqr_stride = per_game ? blk : 0;
     H->lqr_set = true;
+    H->cost_knots = 0;
     sched_drop(H, sched_slot(ALG_SCHED_LQR_TARGET));   // the target schedule goes with the data it was set against
     return ALG_OK;
 }
@@ -1252,6 +1290,23 @@ int alg_get_violation_profile(alg_handle* h, double* dyn, double* con, double* s
     if (sta && (rc = d2h_seg(H, sta, d + 2 * K, per, sizeof(double) * p.N))) return rc;
     if (opt && (rc = d2h_seg(H, opt, d + 2 * K + p.N, per, sizeof(double) * p.N))) return rc;
     return sync(H);
+}
+
+// Players' costs of the plan (k_player_cost): [total | stage] in the inspection scratch, one launch, one copy back per output
+int alg_get_cost(alg_handle* h, int32_t which, double* total, double* stage) {
+    NEED_HANDLE("alg_get_cost");
+    if (which != ALG_TRAJ_PD && which != ALG_TRAJ_TRIAL) return fail(ALG_ERR_ARG, "alg_get_cost: which must be ALG_TRAJ_PD or ALG_TRAJ_TRIAL");
+    if (!total && !stage) return fail(ALG_ERR_ARG, "alg_get_cost: total and stage are both null");
+    if (!H->lqr_set) return fail(ALG_ERR_STATE, "alg_get_cost: LQR data not set");
+    int rc = use_device(H); if (rc) return rc;
+    const Params& p = H->pr;
+    const size_t b_tot = total ? sizeof(double) * (size_t)p.B * p.p * 3 : 0, b_stg = stage ? sizeof(double) * (size_t)p.B * p.N * p.p * 3 : 0;
+    if ((rc = ensure_scratch(H, b_tot + b_stg))) return rc;
+    char* const d = (char*)H->d_scratch;
+    LAUNCH(k_player_cost, H->pr, (int)which, (double*)(total ? d : nullptr), (double*)(stage ? d + b_tot : nullptr));
+    if (total && (rc = d2h(H, total, d, b_tot))) return rc;
+    if (stage && (rc = d2h(H, stage, d + b_tot, b_stg))) return rc;
+    return ALG_OK;
 }
 
 int alg_newton_direction(alg_handle* h, double reg, double* delta, int32_t* status) {
@@ -1536,6 +1591,37 @@ int alg_mpc_solve(alg_handle* h, int32_t steps, int64_t game_id0, double* states
 int alg_mpc_solve_log(alg_handle* h, int32_t steps, int64_t game_id0, double* states, double* controls, alg_game_stats* stats) {
     return mpc_solve_impl("alg_mpc_solve_log", h, steps, game_id0, states, controls, stats);
 }
+// The closed-loop cost log of the fused loop (include/algames_hip.h): mpc_solve_impl fills it, k_closed_loop_cost evaluates it
+int alg_mpc_set_cost_log(alg_handle* h, int32_t on) {
+    NEED_HANDLE("alg_mpc_set_cost_log");
+    if (!on && H->d_cost) {
+        int rc = use_device(H); if (rc) return rc;
+        if ((rc = sync(H))) return rc;             // a loop that writes the log may still run
+        dfree(H, H->d_cost);
+        H->d_cost = nullptr; H->cost_cap = 0;
+    }
+    if (!on) H->cost_knots = 0;
+    H->cost_log = on != 0;
+    return ALG_OK;
+}
+int alg_mpc_get_cost_log(alg_handle* h, int32_t* on) {
+    if (!h || !on) return fail(ALG_ERR_ARG, "alg_mpc_get_cost_log: null argument");
+    *on = H->cost_log ? 1 : 0; return ALG_OK;
+}
+int alg_mpc_get_cost(alg_handle* h, int32_t max_knots, double* stage, double* total, int32_t* knots_out) {
+    if (!h || !knots_out) return fail(ALG_ERR_ARG, "alg_mpc_get_cost: null argument");
+    if (max_knots < 0) return fail(ALG_ERR_ARG, "alg_mpc_get_cost: max_knots must be >= 0");
+    *knots_out = 0;
+    if (!H->cost_log || !H->cost_knots) return ALG_OK;
+    int rc = use_device(H); if (rc) return rc;
+    const Params& p = H->pr;
+    const size_t per = (size_t)p.B * p.p * 3, rows = (size_t)std::min<int>(max_knots, H->cost_knots);
+    if (stage && rows && (rc = d2h(H, stage, H->d_cost, sizeof(double) * rows * per))) return rc;
+    if (total && (rc = d2h(H, total, H->d_cost + (size_t)H->cost_knots * per, sizeof(double) * per))) return rc;
+    if ((rc = sync(H))) return rc;
+    *knots_out = H->cost_knots;
+    return ALG_OK;
+}
 // Schedules of alg_mpc_solve: per game and per MPC step values of one kind (include/algames_hip.h)
 int alg_mpc_set_schedule(alg_handle* h, int32_t kind, int32_t rows, const double* data) {
     static const char* who = "alg_mpc_set_schedule";
@@ -1545,7 +1631,7 @@ int alg_mpc_set_schedule(alg_handle* h, int32_t kind, int32_t rows, const double
     if (!target && !scen_kind_ok(kind)) return fail(ALG_ERR_ARG, "alg_mpc_set_schedule: unknown kind (an ALG_SCEN_* value, ALG_SCHED_LQR_TARGET or ALG_SCHED_DISTURBANCE)");
     const int slot = sched_slot(kind);
     int rc = use_device(H); if (rc) return rc;
-    if (!data) { sched_drop(H, slot); return ALG_OK; }
+    if (!data) { sched_drop(H, slot); H->cost_knots = 0; return ALG_OK; }
     if (rows < 1) return fail(ALG_ERR_ARG, "alg_mpc_set_schedule: rows must be >= 1");
     const Params& p = H->pr;
     std::vector<int> map;
@@ -1588,6 +1674,7 @@ int alg_mpc_set_schedule(alg_handle* h, int32_t kind, int32_t rows, const double
     sc.data.assign(data, data + cnt); sc.map = map;
     sched_drop(H, slot);
     H->sched[slot] = std::move(sc);
+    H->cost_knots = 0;
     return ALG_OK;
 }
 int alg_mpc_get_schedule(alg_handle* h, int32_t kind, int32_t* rows) {

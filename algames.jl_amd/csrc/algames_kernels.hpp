@@ -607,6 +607,9 @@ __global__ void __launch_bounds__(WAVE, C::WPE) k_kkt_solve(Params pr_arg, doubl
     if (so && phase_lane() == 0) as_global(so)[phase_int(gl)] = worst;
 }
 
+// Players' costs of a plan and of a closed-loop run (k_player_cost, k_closed_loop_cost)
+#include "algames_cost.hpp"
+
 // ------------------------------------------------------------------------------------------------
 // Instantiation lists: X(model, p, d, ext)
 // ------------------------------------------------------------------------------------------------
@@ -780,8 +783,12 @@ __global__ void __launch_bounds__(WAVE, C::WPE) k_kkt_solve(Params pr_arg, doubl
 #define ALG_DEFINE_SCHED(M, P, D, E) ALG_INSTANTIATE_SCHED(template, M, P, D, E)
 #define ALG_DECLARE_SCHED(M, P, D, E) ALG_INSTANTIATE_SCHED(extern template, M, P, D, E)
 #define ALG_DEFINE_SCHED_MW(M, P, D, E, W) ALG_INSTANTIATE_SCHED_MW(template, M, P, D, E, W)
-// The step-wise plant knot (k_mpc_plant_advance): one per one-wavefront configuration (ALG_CFGS_ONE), in a unit of their own
-#define ALG_INSTANTIATE_PLANT(PREFIX, M, P, D, E) PREFIX __global__ void k_mpc_plant_advance<Cfg<M, P, D, E>>(Params, int, MpcPlant);
+// The step-wise plant knot (k_mpc_plant_advance): one per one-wavefront configuration (ALG_CFGS_ONE), in a unit of their own -- with the two
+// cost kernels of algames_cost.hpp (k_player_cost, k_closed_loop_cost: one wavefront per game for every handle, like the plant knot)
+#define ALG_INSTANTIATE_PLANT(PREFIX, M, P, D, E)                                                                          \
+    PREFIX __global__ void k_mpc_plant_advance<Cfg<M, P, D, E>>(Params, int, MpcPlant);                                    \
+    PREFIX __global__ void k_player_cost<Cfg<M, P, D, E>>(Params, int, double*, double*);                                  \
+    PREFIX __global__ void k_closed_loop_cost<Cfg<M, P, D, E>>(Params, CostLoopArgs);
 #define ALG_DEFINE_PLANT(M, P, D, E) ALG_INSTANTIATE_PLANT(template, M, P, D, E)
 #define ALG_DECLARE_PLANT(M, P, D, E) ALG_INSTANTIATE_PLANT(extern template, M, P, D, E)
 #define ALG_DECLARE_SCHED_MW(M, P, D, E, W) ALG_INSTANTIATE_SCHED_MW(extern template, M, P, D, E, W)

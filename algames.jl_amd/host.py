@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import (ALG_MODEL_BICYCLE, ALG_MODEL_DOUBLE_INTEGRATOR, ALG_MODEL_QUADROTOR, ALG_MODEL_UNICYCLE, ALG_TRAJ_PD, ALG_TRAJ_TRIAL,
-                   ALG_TRAJ_DELTA, ALG_SCHED_LQR_TARGET, ALG_SCHED_DISTURBANCE, AlgamesError, Batch, CLib, Plant)
+                   ALG_TRAJ_DELTA, ALG_SCEN_COLLISION_COST, ALG_SCHED_LQR_TARGET, ALG_SCHED_DISTURBANCE, AlgamesError, Batch, CLib, Plant)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.environ.get("ALGAMES_HIP_LIB", os.path.join(_HERE, "lib", "libalgames_hip.so"))
@@ -1075,6 +1075,59 @@ def violation_profile(prob):
     return prob.batch.violation_profile()
 
 
+def player_costs(prob, which="pd", stage=False):
+    """What the plan costs each player, evaluated on the device (alg_get_cost): (B, p, 3) with the components [state, control, collision]
+    of J_i = sum_k w_k l_i(x_k, u_k) -- the LQRCost objectives (objective.jl:12-35) and the CollisionCost's stage_cost (objective.jl:122-131)
+    with the weights of the cost gradients, w_k = dt for k < N and w_N = 1; constraints, multipliers and penalties do not enter.
+    which: "pd" (prob.pdtraj) or "trial" (prob.pdtraj_trial).  stage=True also returns the summands per knot: (total, stage (B, N, p, 3))."""
+    code = {"pd": ALG_TRAJ_PD, "trial": ALG_TRAJ_TRIAL}.get(which, which) if isinstance(which, str) else which
+    if isinstance(code, str):
+        raise ValueError(f"player_costs: which must be 'pd' or 'trial', got {which!r}")
+    return prob.batch.get_cost(code, stage=stage)
+
+
+def _stage_cost(b, x, u, Q, R, xf, uf, rad, mu):
+    """l_i of the cost definition (alg_get_cost) in numpy, unweighted: x (B, n); u (B, m) player-major, or None at a terminal knot; Q, xf
+    (B, p, ni); R, uf (B, p, mi); rad, mu (B, p), or None without a collision cost.  Returns (B, p, 3) [state, control, collision]."""
+    p = b.p
+    xi = x.reshape(-1, b.ni, p).transpose(0, 2, 1)                  # pz_i[a] = a p + i
+    out = np.zeros((x.shape[0], p, 3))
+    out[..., 0] = 0.5 * np.sum(Q * (xi - xf) ** 2, axis=-1)
+    if u is not None:
+        out[..., 1] = 0.5 * np.sum(R * (u.reshape(-1, p, b.mi) - uf) ** 2, axis=-1)
+    if rad is not None and p > 1:
+        pos = xi[..., :2]                                           # px_i: entries i and p + i of the joint state
+        dist = np.linalg.norm(pos[:, :, None, :] - pos[:, None, :, :], axis=-1)
+        pen = np.maximum(0.0, rad[:, :, None] - dist) ** 2
+        pen[:, np.arange(p), np.arange(p)] = 0.0
+        out[..., 2] = 0.5 * mu * pen.sum(axis=-1)
+    return out
+
+
+def _cost_numbers(prob, sched, t):
+    """the numbers the running cost of solve t's knots is taken with (alg_mpc_get_cost): Q, R as set; xf, uf and the collision cost's
+    radius, mu from row min(t, rows - 1) of their schedules where scheduled, else the problem's"""
+    b, obj = prob.batch, prob.game_obj
+    full = lambda a, w: np.broadcast_to(np.asarray(a, dtype=np.float64), (b.B, b.p, w))
+    Q, R, xf, uf = full(obj.Qdiag, b.ni), full(obj.Rdiag, b.mi), full(obj.xf, b.ni), full(obj.uf, b.mi)
+    rad = mu = None
+    if obj.collision_radius is not None:
+        if "get_scenario_data" not in getattr(b.lib, "absent", ()):
+            cc = b.get_scenario_data(ALG_SCEN_COLLISION_COST)       # what the handle holds: the games' blocks or the shared values
+            rad, mu = cc[:, :b.p], cc[:, b.p:]
+        else:
+            rad = np.broadcast_to(np.asarray(obj.collision_radius, dtype=np.float64), (b.B, b.p))
+            mu = np.broadcast_to(np.asarray(obj.collision_μ, dtype=np.float64), (b.B, b.p))
+    for k, a in sched:
+        row = a[min(t, a.shape[0] - 1)]
+        if k == ALG_SCHED_LQR_TARGET:
+            w = b.p * b.ni
+            xf, uf = row[:, :w].reshape(b.B, b.p, b.ni), row[:, w:].reshape(b.B, b.p, b.mi)
+        elif k == ALG_SCEN_COLLISION_COST:
+            rad, mu = row[:, :b.p], row[:, b.p:]
+    return Q, R, xf, uf, rad, mu
+
+
 def dynamics_violation(prob):
     return prob.batch.record()["dyn_vio"]
 
@@ -1232,15 +1285,19 @@ class MpcRollout:
     """Closed-loop log of mpc_rollout over steps solves and knots = steps * hold plant knots (hold = 1 without a plant): states
     (knots+1, B, n) -- x0 before the loop and after every knot, disturbed where a disturbance acts --, controls (knots, B, m) -- the joint
     control every knot held, player-major --, stats (steps, B) of game_stats_dtype -- every step's solve as get_stats reports it --, and the
-    totals newton_iters (B,), converged (B,), which gain every solve once."""
+    totals newton_iters (B,), converged (B,), which gain every solve once.  With costs=True also stage_cost (knots, B, p, 3) -- the running
+    cost dt l_i(states[q], controls[q]) of every knot and player in the components [state, control, collision] of player_costs, taken with
+    the schedule rows the knot's solve used -- and cost (B, p, 3), its sum over the knots (no terminal term); None otherwise."""
     states: np.ndarray
     controls: np.ndarray
     stats: np.ndarray
     newton_iters: np.ndarray
     converged: np.ndarray
+    stage_cost: np.ndarray = None
+    cost: np.ndarray = None
 
 
-def mpc_rollout(prob, steps=None, schedule=None, disturbance=None, fused=True, plant=None):
+def mpc_rollout(prob, steps=None, schedule=None, disturbance=None, fused=True, plant=None, costs=False):
     """The receding-horizon loop as a closed-loop simulation: mpc_solve's loop with every step observable and a disturbed plant.  Returns
     an MpcRollout.  steps=None takes prob.opts.mpc_horizon.
 
@@ -1252,7 +1309,10 @@ def mpc_rollout(prob, steps=None, schedule=None, disturbance=None, fused=True, p
     solve is warm-started with shift = hold.  Without a plant a knot is a step: q = t.
     fused=True: one launch (alg_mpc_solve_log; schedule and disturbance are uploaded and dropped again); fused=False: the definition --
     per step the schedule rows, newton_solve_async, get_stats and the controls of get_traj, then per knot mpc_plant_advance(j) (mpc_advance
-    without a plant), x0 read back, set_x0(x0 + w_q)."""
+    without a plant), x0 read back, set_x0(x0 + w_q).
+    costs=True: what the run cost each player (MpcRollout.stage_cost, .cost).  fused=True takes them from the device's cost log
+    (Batch.mpc_set_cost_log, switched on for the call); fused=False evaluates the definition in numpy on the states and controls of the log
+    with the rows _apply_schedule_rows applied."""
     b = prob.batch
     if steps is None:
         steps = prob.opts.mpc_horizon
@@ -1273,19 +1333,27 @@ def mpc_rollout(prob, steps=None, schedule=None, disturbance=None, fused=True, p
         if fused:
             up = sched + ([(ALG_SCHED_DISTURBANCE, w)] if w is not None else [])
             done = []
+            log0 = b.mpc_get_cost_log() if costs else None
+            stage_cost = cost = None
             try:
+                if costs:
+                    b.mpc_set_cost_log(True)
                 for k, a in up:
                     b.mpc_set_schedule(k, a)
                     done.append(k)
                 states, controls, stats = b.mpc_solve_log(steps, prob.game_id0)
                 it, cv = b.mpc_totals()
+                if costs:
+                    stage_cost, cost = b.mpc_get_cost()             # before the schedules go: dropping one invalidates the log
             finally:
                 for k in done:
                     b.mpc_set_schedule(k, None)
-            return MpcRollout(states, controls, stats, it, cv)
+                if costs and not log0:
+                    b.mpc_set_cost_log(False)
+            return MpcRollout(states, controls, stats, it, cv, stage_cost, cost)
         shift0, reset0 = prob.opts.shift, prob.opts.dual_reset
         n, m = b.n, b.m
-        states, controls, stats = [b.get_x0()], [], []
+        states, controls, stats, stage_cost = [b.get_x0()], [], [], []
         stepwise_plant = plant is not None or not pl.is_default
         try:
             for t in range(steps):
@@ -1296,9 +1364,12 @@ def mpc_rollout(prob, steps=None, schedule=None, disturbance=None, fused=True, p
                 b.newton_solve_async(init=True, game_id0=prob.game_id0 + t * 1000003)
                 stats.append(b.get_stats())
                 z = b.get_traj()
+                nums = _cost_numbers(prob, sched, t) if costs else None
                 for j in range(pl.hold):
                     q = t * pl.hold + j
                     controls.append(z[:, 2 * n + j * b.b:2 * n + j * b.b + m].copy())
+                    if costs:
+                        stage_cost.append(prob.dt * _stage_cost(b, states[-1], controls[-1], *nums))
                     if stepwise_plant:
                         b.mpc_plant_advance(j)
                     else:
@@ -1312,4 +1383,7 @@ def mpc_rollout(prob, steps=None, schedule=None, disturbance=None, fused=True, p
         finally:
             prob.opts.shift, prob.opts.dual_reset = shift0, reset0
             prob._sync_options()
+        if costs:
+            stage_cost = np.stack(stage_cost)
+            return MpcRollout(np.stack(states), np.stack(controls), np.stack(stats), it, cv, stage_cost, stage_cost.sum(axis=0))
         return MpcRollout(np.stack(states), np.stack(controls), np.stack(stats), it, cv)

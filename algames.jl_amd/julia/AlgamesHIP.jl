@@ -10,6 +10,7 @@
 #   ibr_newton_solve!(bp; ibr_opts), ibr_newton_solve!(bp, i)     solver_methods.jl:133-228
 #   mpc_solve!(bp, steps; schedule)                   receding-horizon loop of BASELINE config 5 (opts.shift / opts.dual_reset), with per-step values of targets / obstacles
 #   mpc_solve_log!(bp, steps; disturbance)            the same loop with the closed-loop log (controls and statistics of every step) and a plant disturbance
+#   player_costs(bp), set_mpc_cost_log!(bp, on), mpc_costs(bp)    what a plan / a closed-loop run costs each player, evaluated on the device
 #   newton_solve!(probs::Vector{<:GameProblem})       convenience: build a handle, solve, release
 #   sp = ShardedGameProblem(probs; devices=0:7); newton_solve!(sp)     the batch split over several devices (one handle each)
 # After a solve every `prob.pdtraj`, the multipliers / penalties / values of every constraint (`conval.λ`, `.μ`, `.vals`,
@@ -636,15 +637,16 @@ function mpc_solve!(bp::BatchedGameProblem, steps::Integer; game_id0::Integer=0,
 end
 
 """
-    mpc_solve_log!(bp, steps; game_id0=0, schedule=nothing, disturbance=nothing) -> (newton_iters, converged, states, controls, stats)
+    mpc_solve_log!(bp, steps; game_id0=0, schedule=nothing, disturbance=nothing, costs=false) -> (newton_iters, converged, states, controls, stats[, costs])
 
 The loop of `mpc_solve!` with the closed-loop log (`alg_mpc_solve_log`): `controls` is m x B x steps (the joint control every advance
 applied, player-major), `stats` a B x steps matrix of `AlgGameStats` (every step's solve as `alg_get_stats` reports it).
 `schedule`: as for `mpc_solve!`.  `disturbance`: n x B x rows, finite -- after the advance of the step-th solve the state becomes
 x0 + slice min(step, rows); `states` holds the disturbed states.  It travels as one more schedule kind (`SCHED_DISTURBANCE`): uploaded
-and dropped again with the others.
+and dropped again with the others.  `costs=true` switches the cost log on for the call (`set_mpc_cost_log!`) and appends `mpc_costs(bp)`,
+read before the schedules are dropped, to the result.
 """
-function mpc_solve_log!(bp::BatchedGameProblem, steps::Integer; game_id0::Integer=0, schedule=nothing, disturbance=nothing)
+function mpc_solve_log!(bp::BatchedGameProblem, steps::Integer; game_id0::Integer=0, schedule=nothing, disturbance=nothing, costs::Bool=false)
     sync_options!(bp)
     B = length(bp.probs); n = bp.probs[1].probsize.n; m = bp.probs[1].probsize.m
     iters = zeros(Int64, B); conv = zeros(Int64, B)
@@ -658,16 +660,24 @@ function mpc_solve_log!(bp::BatchedGameProblem, steps::Integer; game_id0::Intege
         size(W, 1) == n && size(W, 2) == B && size(W, 3) >= 1 || error("mpc_solve_log!: the disturbance must be $n x $B x rows")
         up[SCHED_DISTURBANCE] = W
     end
-    with_schedules(bp, "mpc_solve_log!", up) do
-        check(ccall((:alg_mpc_solve_log, LIB), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{AlgGameStats}),
-                    bp.h, steps, game_id0, states, controls, stats))
+    cost = nothing
+    log0 = costs && mpc_cost_log(bp)
+    costs && set_mpc_cost_log!(bp, true)
+    try
+        with_schedules(bp, "mpc_solve_log!", up) do
+            check(ccall((:alg_mpc_solve_log, LIB), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{AlgGameStats}),
+                        bp.h, steps, game_id0, states, controls, stats))
+            costs && (cost = mpc_costs(bp))
+        end
+    finally
+        costs && !log0 && set_mpc_cost_log!(bp, false)
     end
     check(ccall((:alg_mpc_totals, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Int32), bp.h, iters, conv, 0))
     pull_results!(bp, stats[:, end])                                # the last solve's iterate, multipliers and statistics
     for (g, pr) in enumerate(bp.probs)
         pr.x0 = SVector{n}(states[:, g, end])
     end
-    return iters, conv, states, controls, stats
+    return costs ? (iters, conv, states, controls, stats, cost) : (iters, conv, states, controls, stats)
 end
 
 # ---- step-wise entry points on a handle (same names as the reference's functions they batch) ------------------------------------
@@ -726,6 +736,51 @@ function direction_gate(bp::BatchedGameProblem)
     out = zeros(3, length(bp.probs))
     check(ccall((:alg_get_direction_gate, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}), bp.h, out))
     return out
+end
+
+"""
+    player_costs(bp; trial=false, stage=false) -> total [, stage]
+
+What the plan costs each player, evaluated on the device (alg_get_cost): `total` is 3 x p x B -- the components [state, control, collision]
+of J_i = sum_k w_k l_i(x_k, u_k), the values of the `LQRCost` objectives (objective.jl:12-35) and of `stage_cost(::CollisionCost, x)`
+(objective.jl:122-131) with w_k = dt for k < N and w_N = 1; constraints, multipliers and penalties do not enter.  `trial=true` evaluates
+`pdtraj_trial`; `stage=true` also returns the summands per knot, 3 x p x N x B.  Nothing on the handle changes.
+"""
+function player_costs(bp::BatchedGameProblem; trial::Bool=false, stage::Bool=false)
+    B = length(bp.probs); p = bp.probs[1].probsize.p; N = bp.probs[1].probsize.N
+    total = zeros(3, p, B)
+    stg = stage ? zeros(3, p, N, B) : nothing
+    check(ccall((:alg_get_cost, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}), bp.h, trial ? 1 : 0, total, stage ? stg : C_NULL))
+    return stage ? (total, stg) : total
+end
+"""
+    set_mpc_cost_log!(bp, on)
+
+The closed-loop cost log of `mpc_solve!` / `mpc_solve_log!` (alg_mpc_set_cost_log; off by default): with it on the loop also evaluates, on the
+device, what every plant knot cost every player -- with the schedule rows the knot's solve used.  `mpc_costs(bp)` reads it.
+"""
+set_mpc_cost_log!(bp::BatchedGameProblem, on::Bool) = check(ccall((:alg_mpc_set_cost_log, LIB), Cint, (Ptr{Cvoid}, Int32), bp.h, on ? 1 : 0))
+function mpc_cost_log(bp::BatchedGameProblem)
+    on = Ref{Int32}(0)
+    check(ccall((:alg_mpc_get_cost_log, LIB), Cint, (Ptr{Cvoid}, Ref{Int32}), bp.h, on))
+    return on[] != 0
+end
+"""
+    mpc_costs(bp) -> (stage, total) or nothing
+
+The cost log of the most recent `mpc_solve!` / `mpc_solve_log!` (alg_mpc_get_cost): `stage` is 3 x p x B x knots -- the running cost
+dt l_i(states[q], controls[q]) in the components [state, control, collision] --, `total` 3 x p x B its sum over the knots (no terminal term).
+`nothing` while there is none: log off, no loop yet, or invalidated by an adder, new LQR or scenario data, or a schedule call.  (The loop
+entry points drop their schedules when they return, which invalidates the log: `mpc_solve_log!(...; costs=true)` reads it before that.)
+"""
+function mpc_costs(bp::BatchedGameProblem)
+    B = length(bp.probs); p = bp.probs[1].probsize.p
+    knots = Ref{Int32}(0)
+    check(ccall((:alg_mpc_get_cost, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ref{Int32}), bp.h, 0, C_NULL, C_NULL, knots))
+    knots[] == 0 && return nothing
+    stage = zeros(3, p, B, Int(knots[])); total = zeros(3, p, B)
+    check(ccall((:alg_mpc_get_cost, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ref{Int32}), bp.h, knots[], stage, total, knots))
+    return stage, total
 end
 
 "Give the inspection entry points' device scratch (dense Jacobians, MPC state logs) back to the allocator."

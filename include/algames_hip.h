@@ -369,6 +369,23 @@ int alg_release_scratch(alg_handle* h);
  * sta, opt: B x N (knots 1..N; sta[0] is 0: no state constraint acts on x_1).  Any pointer may be NULL.  Evaluated on the device
  * from the residual and the constraint values at the current pdtraj (one assemble pass + one reduction kernel). */
 int alg_get_violation_profile(alg_handle* h, double* dyn, double* con, double* sta, double* opt);
+/* What the plan costs each player: the values of the GameObjective whose gradients the solver assembles -- LQRCost (objective.jl:12-35)
+ * and CollisionCost, TrajectoryOptimization.stage_cost(::CollisionCost, x) (objective.jl:122-131).  The objective itself: constraints,
+ * multipliers and penalties do not enter.  Player i of one game:
+ *   J_i = sum_{k=1..N} w_k l_i(x_k, u_k),  w_k = dt for k < N, w_N = 1 (the weights of the cost gradients), l_i in three components:
+ *     state      1/2 sum_a Q_i[a] (x[pz_i[a]] - xf_i[a])^2 over the player's own ni state entries (alg_set_lqr layout); every knot, x_1 included
+ *     control    1/2 sum_a R_i[a] (u[pu_i[a]] - uf_i[a])^2; 0 at k = N
+ *     collision  sum_{j != i} 1/2 mu_i max(0, r_i - |px_i - px_j|)^2 with the two position entries and the (mu_i, r_i) the collision-cost
+ *                gradient uses -- the handle's values or the game's scenario block, in both alg_set_scenario_kernels modes; the planar
+ *                distance for every model; 0 without alg_add_collision_cost
+ * which: ALG_TRAJ_PD or ALG_TRAJ_TRIAL.  total: B x p x 3 [state, control, collision]; stage: B x N x p x 3, knot-major within a game, the
+ * summands w_k l_i (they add up to total to rounding); either may be NULL, not both.
+ * One launch, one wavefront per game whatever kernels the handle solves with; a game's numbers do not depend on the batch size or on its
+ * place in the batch, bit for bit.  Non-finite input gives non-finite output for that game only; no status is set.
+ * ALG_ERR_ARG, with nothing changed, for a null handle, another `which` or two null outputs; ALG_ERR_STATE if alg_set_lqr was not called.
+ * The call changes nothing on the handle: trajectories, multipliers, statistics, history, profiles, step records and the direction-gate
+ * figures stay as they are.  Uses the inspection scratch (alg_release_scratch). */
+int alg_get_cost(alg_handle* h, int32_t which /* ALG_TRAJ_PD | ALG_TRAJ_TRIAL */, double* total /* B x p x 3, or NULL */, double* stage /* B x N x p x 3, or NULL */);
 /* Δtraj = -lu(jac) \ res ; set_traj!(Δpdtraj, Δtraj) (solver_methods.jl:87-88).  delta: B x S or NULL. */
 int alg_newton_direction(alg_handle* h, double reg, double* delta, int32_t* status /*B or NULL*/);
 /* KKT solves with many right-hand sides at the current iterate: J X = R with J the (regularised) residual Jacobian of
@@ -552,6 +569,27 @@ typedef struct alg_mpc_plant { int32_t hold, substeps, integrator, reserved; } a
 int alg_mpc_set_plant(alg_handle* h, const alg_mpc_plant* p /* NULL = default */);
 int alg_mpc_get_plant(alg_handle* h, alg_mpc_plant* p);
 int alg_mpc_plant_advance(alg_handle* h, int32_t knot);
+/* The closed-loop COST LOG of the fused loop: what the run cost each player, evaluated on the device.  States and controls alone do not
+ * determine it: the running cost of a knot depends on the schedule row its solve used and on per-game numbers that live on the device.
+ * With the log on (default off) alg_mpc_solve / alg_mpc_solve_log keep the state and control logs on the device whether or not the caller asks
+ * for them (the loop kernels with per-step phases, as for any log) and queue one more kernel behind the loop, on the same stream: a call with
+ * three NULL output pointers stays asynchronous.  Plant knot q = t*hold + j of solve t, player i:
+ *   stage[q][g][i] = dt * l_i(states[q][g], controls[q][g]), the three components of alg_get_cost's l_i (LQRCost objective.jl:12-35,
+ *   CollisionCost objective.jl:122-131): states[q] is the state at the beginning of the knot (the disturbance of the knot before included),
+ *   controls[q] the control held, read through pu_i of the stored player-major order.  xf, uf: row min(t, rows - 1) of the
+ *   ALG_SCHED_LQR_TARGET schedule if one is set, else the handle's; mu, r: row min(t, rows - 1) of an ALG_SCEN_COLLISION_COST schedule if one
+ *   is set, else the game's block or the handle's values; Q and R as set.  No terminal term: states[knots] is not costed.
+ *   total[g][i] = sum_q stage[q][g][i], per component.
+ * States, controls, statistics, totals and everything the loop leaves on the handle are bit-identical with the log on and off.
+ * The log lives in a buffer of the handle's own, (knots + 1) x B x p x 3 doubles, grown on demand and freed when the log is switched off; a
+ * run whose log would exceed 1 GiB is refused with ALG_ERR_ARG before anything is launched.
+ * alg_mpc_get_cost waits for the stream.  *knots_out = the plant knots of the most recent alg_mpc_solve / alg_mpc_solve_log; stage receives
+ * the first min(max_knots, *knots_out) of them (knots x B x p x 3), total B x p x 3; either may be NULL.  The log belongs to that loop and
+ * to the data it ran with: any adder (alg_add_*), alg_set_lqr, alg_set_scenario_data and alg_mpc_set_schedule invalidate it -- *knots_out = 0
+ * and nothing is written -- until the next loop.  With the log off: ALG_OK and *knots_out = 0.  IBR and the step-wise MPC calls have no log. */
+int alg_mpc_set_cost_log(alg_handle* h, int32_t on);
+int alg_mpc_get_cost_log(alg_handle* h, int32_t* on);
+int alg_mpc_get_cost(alg_handle* h, int32_t max_knots, double* stage /* knots x B x p x 3, or NULL */, double* total /* B x p x 3, or NULL */, int32_t* knots_out);
 
 #ifdef __cplusplus
 }
