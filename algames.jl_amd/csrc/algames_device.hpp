@@ -456,31 +456,40 @@ __device__ __forceinline__ void bike_coefs(CPR pr, double v, double psi, double 
     cf[4] = dt * g.sg; cf[5] = dt * cs; cf[6] = dt * sn;
     cf[7] = -dt * vm * sn * dth; cf[8] = dt * vm * cs * dth; cf[9] = dt * vm * g.dsg;
 }
+// The continuous dynamics of one player on its own entries (s[ni], ui[mi]): the f of the roll-out's RK3 and of the plant's RK4
 template <class C>
-__device__ __forceinline__ void model_player(CPR pr, int i, const double* x, const double* u, double dt,
-                                             double* xn /*ni: entries pz(i,j)*/, double* coef /*4: entries j*P+i (unicycle only)*/) {
+__device__ __forceinline__ void model_f(CPR pr, const double (&s)[C::ni], const double (&ui)[C::mi], double (&o)[C::ni]) {
     if constexpr (C::QUAD) {
-        double xi[12], ui[4], xo[12];
-#pragma unroll
-        for (int j = 0; j < 12; j++) xi[j] = x[i + j * C::P];
-#pragma unroll
-        for (int j = 0; j < 4; j++) ui[j] = u[i + j * C::P];
-        quad_rk2(xi, ui, pr.qmass, dt, xo);
-#pragma unroll
-        for (int j = 0; j < 12; j++) xn[j] = xo[j];
-        coef[0] = coef[1] = coef[2] = coef[3] = 0.0;
+        quad_f(s, ui, pr.qmass, o);
     } else if constexpr (C::MODEL == ALG_MODEL_DOUBLE_INTEGRATOR) {
 #pragma unroll
+        for (int j = 0; j < C::D; j++) { o[j] = s[C::D + j]; o[C::D + j] = ui[j]; }
+    } else if constexpr (C::MODEL == ALG_MODEL_BICYCLE) {
+        const BikeGeom g = bike_geom(ui[1], pr.lf, pr.lr);
+        double sn, cs; sincos(g.beta + s[3], &sn, &cs);
+        o[0] = s[2] * cs; o[1] = s[2] * sn; o[2] = ui[0]; o[3] = s[2] * g.sg;
+    } else {
+        double sn, cs; sincos(s[2], &sn, &cs);
+        o[0] = cs * s[3]; o[1] = sn * s[3]; o[2] = ui[0]; o[3] = ui[1];
+    }
+}
+// The model's discrete step of one player: RK2 (explicit midpoint, RobotDynamics 0.3.1: k1 = f(x,u) dt ; xm = x + k1/2 ; k2 = f(xm,u) dt ;
+// x + k2) on joint arrays x, u indexed by the player i, as mpc_advance holds them; the quadrotor's is quad_rk2 above.  (The plant keeps a
+// restatement on the player's own compact arrays, plant_rk2 in algames_kernels.hpp: routed through this function with a stride of 1 it
+// compiled to other code in one scheduled loop kernel, profiles/model_equations_isa.txt.)
+template <class C>
+__device__ __forceinline__ void model_rk2(CPR pr, int i, const double* x, const double* u, double dt, double (&xn)[C::ni]) {
+    constexpr int P = C::P;
+    static_assert(!C::QUAD, "the quadrotor steps through quad_rk2 on its own arrays (mpc_advance)");
+    if constexpr (C::MODEL == ALG_MODEL_DOUBLE_INTEGRATOR) {
+#pragma unroll
         for (int j = 0; j < C::D; j++) {
-            const int ip = i + j * C::P, iv = C::m + i + j * C::P;
-            // k1 = f(x,u) dt ; xm = x + k1/2 ; k2 = f(xm,u) dt ; x + k2   (RobotDynamics 0.3.1 RK2)
+            const int ip = i + j * P, iv = C::m + i + j * P;
             const double vm = x[iv] + (u[ip] * dt) * 0.5;
             xn[j] = x[ip] + vm * dt;
             xn[C::D + j] = x[iv] + u[ip] * dt;
         }
-        coef[0] = coef[1] = coef[2] = coef[3] = 0.0;
     } else if constexpr (C::MODEL == ALG_MODEL_BICYCLE) {
-        const int P = C::P;
         const double v = x[2 * P + i], psi = x[3 * P + i], a = u[i];
         const BikeGeom g = bike_geom(u[P + i], pr.lf, pr.lr);
         const double vm = v + (a * dt) * 0.5, psm = psi + (v * g.sg * dt) * 0.5;
@@ -489,9 +498,7 @@ __device__ __forceinline__ void model_player(CPR pr, int i, const double* x, con
         xn[1] = x[P + i] + (vm * s) * dt;
         xn[2] = v + a * dt;
         xn[3] = psi + (vm * g.sg) * dt;
-        coef[0] = coef[1] = coef[2] = coef[3] = 0.0;
     } else {
-        const int P = C::P;
         const double th = x[2 * P + i], v = x[3 * P + i], om = u[i], a = u[P + i];
         const double thm = th + (om * dt) * 0.5, vm = v + (a * dt) * 0.5;
         double s, c;
@@ -500,36 +507,21 @@ __device__ __forceinline__ void model_player(CPR pr, int i, const double* x, con
         xn[1] = x[P + i] + (s * vm) * dt;
         xn[2] = th + om * dt;
         xn[3] = v + a * dt;
-        coef[0] = -dt * vm * s; coef[1] = dt * c; coef[2] = dt * vm * c; coef[3] = dt * s;
     }
 }
 // RK3 step of player i (rollout!, solver_methods.jl:17; RobotDynamics 0.3.1 RK3)
-// (the player's own entries as compact arrays xi[ni], ui[mi]: the roll-out keeps its state in this form -- a joint array indexed by the lane's
-// player number is a register array with a run-time index, i.e. a select chain over n compare masks per access)
+// (the player's own entries as compact arrays xi[ni], ui[mi])
 template <class C>
 __device__ __forceinline__ void model_player_rk3_own(CPR pr, const double (&xi)[C::ni], const double (&ui)[C::mi], double dt, double* xn) {
     static_assert(!C::QUAD, "the quadrotor integrates through quad_rk3 (rollout)");
     double k1[C::ni], k2[C::ni], k3[C::ni], t[C::ni];
-    auto f = [&](const double* s, double* o) {
-        if constexpr (C::MODEL == ALG_MODEL_DOUBLE_INTEGRATOR) {
-#pragma unroll
-            for (int j = 0; j < C::D; j++) { o[j] = s[C::D + j]; o[C::D + j] = ui[j]; }
-        } else if constexpr (C::MODEL == ALG_MODEL_BICYCLE) {
-            const BikeGeom g = bike_geom(ui[1], pr.lf, pr.lr);
-            double sn, cs; sincos(g.beta + s[3], &sn, &cs);
-            o[0] = s[2] * cs; o[1] = s[2] * sn; o[2] = ui[0]; o[3] = s[2] * g.sg;
-        } else {
-            double sn, cs; sincos(s[2], &sn, &cs);
-            o[0] = cs * s[3]; o[1] = sn * s[3]; o[2] = ui[0]; o[3] = ui[1];
-        }
-    };
-    f(xi, k1);
+    model_f<C>(pr, xi, ui, k1);
 #pragma unroll
     for (int j = 0; j < C::ni; j++) { k1[j] *= dt; t[j] = xi[j] + k1[j] / 2; }
-    f(t, k2);
+    model_f<C>(pr, t, ui, k2);
 #pragma unroll
     for (int j = 0; j < C::ni; j++) { k2[j] *= dt; t[j] = xi[j] - k1[j] + 2 * k2[j]; }
-    f(t, k3);
+    model_f<C>(pr, t, ui, k3);
 #pragma unroll
     for (int j = 0; j < C::ni; j++) { k3[j] *= dt; xn[j] = xi[j] + (k1[j] + 4 * k2[j] + k3[j]) / 6; }
 }

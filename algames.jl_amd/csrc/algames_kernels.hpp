@@ -192,10 +192,10 @@ __device__ __forceinline__ void mpc_advance(CPR pr, const Game& G) {
             for (int j = 0; j < 12; j++) { const int a = lane + j * C::P; G.x0w(pr)[a] = xo[j]; G.z(0)[a] = xo[j]; G.z(1)[a] = xo[j]; }
         }
     } else if (lane < C::P) {
-        double x[C::n], u[C::m], xo[C::ni], co[4];
+        double x[C::n], u[C::m], xo[C::ni];
         for (int j = 0; j < C::ni; j++) x[lane + j * C::P] = G.z(0)[lane + j * C::P];
         for (int j = 0; j < C::mi; j++) u[lane + j * C::P] = G.z(0)[C::n + hu<C>(0, lane) + j];
-        model_player<C>(pr, lane, x, u, pr.dt, xo, co);
+        model_rk2<C>(pr, lane, x, u, pr.dt, xo);
         for (int j = 0; j < C::ni; j++) {
             const int a = lane + j * C::P;
             G.x0w(pr)[a] = xo[j]; G.z(0)[a] = xo[j]; G.z(1)[a] = xo[j];
@@ -336,24 +336,7 @@ __device__ __forceinline__ void mpc_disturb(CPR pr, const Game& G, const ALG_AS4
 struct MpcPlant { int hold, substeps, integrator, pad_; };
 struct MpcLoopSchedArgs { Params pr; int steps; uint64_t game_id0; double* states; MpcSched sd; MpcLoopLog lg; MpcPlant pl; };
 __host__ __device__ inline bool mpc_plant_is_default(int hold, int substeps, int integrator) { return hold == 1 && substeps == 1 && integrator == ALG_PLANT_RK2; }
-// the continuous dynamics of one player on its own entries (the f of model_player_rk3_own / quad_f)
-template <class C>
-__device__ __forceinline__ void plant_f(CPR pr, const double (&s)[C::ni], const double (&ui)[C::mi], double (&o)[C::ni]) {
-    if constexpr (C::QUAD) {
-        quad_f(s, ui, pr.qmass, o);
-    } else if constexpr (C::MODEL == ALG_MODEL_DOUBLE_INTEGRATOR) {
-#pragma unroll
-        for (int j = 0; j < C::D; j++) { o[j] = s[C::D + j]; o[C::D + j] = ui[j]; }
-    } else if constexpr (C::MODEL == ALG_MODEL_BICYCLE) {
-        const BikeGeom g = bike_geom(ui[1], pr.lf, pr.lr);
-        double sn, cs; sincos(g.beta + s[3], &sn, &cs);
-        o[0] = s[2] * cs; o[1] = s[2] * sn; o[2] = ui[0]; o[3] = s[2] * g.sg;
-    } else {
-        double sn, cs; sincos(s[2], &sn, &cs);
-        o[0] = cs * s[3]; o[1] = sn * s[3]; o[2] = ui[0]; o[3] = ui[1];
-    }
-}
-// the model's own discrete step (model_player, quad_rk2) on the player's own entries: the same expressions, entry for entry
+// the model's own discrete step (model_rk2, quad_rk2) on the player's own entries: the same expressions, entry for entry
 template <class C>
 __device__ __forceinline__ void plant_rk2(CPR pr, const double (&xi)[C::ni], const double (&ui)[C::mi], const double dt, double (&xn)[C::ni]) {
     if constexpr (C::QUAD) {
@@ -389,16 +372,16 @@ __device__ __forceinline__ void plant_rk2(CPR pr, const double (&xi)[C::ni], con
 template <class C>
 __device__ __forceinline__ void plant_rk4(CPR pr, const double (&xi)[C::ni], const double (&ui)[C::mi], const double h, double (&xn)[C::ni]) {
     double k[C::ni], acc[C::ni], t[C::ni];
-    plant_f<C>(pr, xi, ui, k);
+    model_f<C>(pr, xi, ui, k);
 #pragma unroll
     for (int j = 0; j < C::ni; j++) { acc[j] = k[j]; t[j] = xi[j] + (h * 0.5) * k[j]; }
-    plant_f<C>(pr, t, ui, k);
+    model_f<C>(pr, t, ui, k);
 #pragma unroll
     for (int j = 0; j < C::ni; j++) { acc[j] = acc[j] + 2.0 * k[j]; t[j] = xi[j] + (h * 0.5) * k[j]; }
-    plant_f<C>(pr, t, ui, k);
+    model_f<C>(pr, t, ui, k);
 #pragma unroll
     for (int j = 0; j < C::ni; j++) { acc[j] = acc[j] + 2.0 * k[j]; t[j] = xi[j] + h * k[j]; }
-    plant_f<C>(pr, t, ui, k);
+    model_f<C>(pr, t, ui, k);
 #pragma unroll
     for (int j = 0; j < C::ni; j++) xn[j] = xi[j] + (h / 6.0) * (acc[j] + k[j]);
 }

@@ -403,10 +403,8 @@ __device__ void dual_penalty_update(CPR pr0, const Game& G0) {
 // (OL: the lane index through an opaque copy -- inside k_mpc_loop the lane predicates of this function were invariants of the receding-horizon
 // loop, live across every solve)
 // (measured in round 6 and not taken: the roll-out on the player's own compact arrays instead of joint arrays indexed by the lane's player number --
-// fewer compare masks in the prologue, but the C3 solve kernel's SGPR spills went 8 -> 13 and the C5 loop kernel's 13 -> 17)
-#ifndef ALG_ROLLOUT_OWN
-#define ALG_ROLLOUT_OWN 0
-#endif
+// fewer compare masks in the prologue, but the C3 solve kernel's SGPR spills went 8 -> 13 and the C5 loop kernel's 13 -> 17; that body went with its
+// build switch and can be rebuilt from the parent of the commit that removed it)
 template <class C, bool OL = false>
 __device__ __forceinline__ void rollout(CPR pr, double* z, double* lds = nullptr, int cap = 0) {
     constexpr int n = C::n, m = C::m, P = C::P;
@@ -431,20 +429,7 @@ __device__ __forceinline__ void rollout(CPR pr, double* z, double* lds = nullptr
                 for (int j = 0; j < 12; j++) { xi[j] = xo[j]; z[n + hx<C>(k) + lane + j * P] = xo[j]; }
             }
         }
-    } else if (ALG_ROLLOUT_OWN && lane < P) {
-        double xi[C::ni], ui[C::mi];     // this player's entries
-#pragma unroll
-        for (int j = 0; j < C::ni; j++) xi[j] = z[lane + j * P];
-        for (int k = 0; k < pr.N - 1; k++) {
-#pragma unroll
-            for (int j = 0; j < C::mi; j++) ui[j] = uget(k, lane, j);
-            double xn[C::ni];
-            model_player_rk3_own<C>(pr, xi, ui, pr.dt, xn);
-#pragma unroll
-            for (int j = 0; j < C::ni; j++) { xi[j] = xn[j]; z[n + hx<C>(k) + lane + j * P] = xn[j]; }
-        }
-    }
-    else if (lane < P) {
+    } else if (lane < P) {
         double x[n], u[m];     // only this player's entries are used
         for (int j = 0; j < C::ni; j++) x[lane + j * P] = z[lane + j * P];
         for (int k = 0; k < pr.N - 1; k++) {

@@ -59,11 +59,14 @@ SHAPES = {
 # the kernels every shape must run on (get_scenario_kernels()[1]): 0 base, 1 EXT (the circle; the bicycle, which is compiled as EXT only),
 # 2 the block-reading twins of the base kernels
 KERNELS = {"di3_one_wavefront": 0, "uni3_team_of_four": 0, "uni3_circle_ext": 1, "di3_base_mode_twin": 2, "bic2": 1, "quad2_team_of_four": 0, "di7_dense": 0}
+# Shapes that build() knows and the tests parametrised over SHAPES do not run: two double integrators on a line (d = 1) and in space (d = 3), the
+# trip counts of the RK2 step's loop over the dimensions that no shape above has (tests/test_gpu_mpc_plant.py, the default plant's advance)
+ADVANCE_SHAPES = {"di2_line": (DI, 2, 1, B, 0, ()), "di2_space": (DI, 2, 3, B, 0, ())}
 
 
 def build(alg, name):
     """(batch, schedule {kind: rows}, disturbance, LQR data for the step-wise target rows) of one shape; deterministic"""
-    model, p, d, nb, waves, extra = SHAPES[name]
+    model, p, d, nb, waves, extra = SHAPES.get(name) or ADVANCE_SHAPES[name]
 
     lqr = {}
 

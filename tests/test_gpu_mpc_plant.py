@@ -110,7 +110,7 @@ def test_the_default_plant_set_explicitly_is_the_loop_without_a_plant(alg, name)
         assert np.array_equal(a, c)
 
 
-@pytest.mark.parametrize("name", ["di3_one_wavefront", "uni3_circle_ext", "di3_base_mode_twin", "bic2", "quad2_team_of_four", "di7_dense"])
+@pytest.mark.parametrize("name", ["di3_one_wavefront", "uni3_circle_ext", "di3_base_mode_twin", "bic2", "quad2_team_of_four", "di7_dense"] + list(LG.ADVANCE_SHAPES))
 def test_plant_advance_of_the_default_plant_is_mpc_advance(alg, name):
     a, c = LG.build(alg, name)[0], LG.build(alg, name)[0]
     for b in (a, c):
