@@ -159,11 +159,11 @@ def name(cfg):
     return HS._name(cfg)
 
 
-def pair(alg, orc, cfg, N, B=4):
+def pair(alg, orc, cfg, N, B=4, seed=None):
     """(product batch, oracle batch, rows) on the random full-magnitude data of the parity tests' _pair, all ingredients on, seed N: every extended
     row with a multiplier of O(1) (three in ten: 0) and a penalty in [1, 3]"""
     model, p, d = cfg
-    seed = PAIR_SEED.get((cfg, N), N)
+    seed = PAIR_SEED.get((cfg, N), N) if seed is None else seed
     if d == 3:
         if cfg == DI2_D3:
             import test_gpu_parity_3d as P3

@@ -88,14 +88,15 @@ FUZZ_TOL = float(__import__("os").environ.get("ALGAMES_FUZZ_TOL", 1e-8))
 FUZZ_TOL_LOOSE = {}
 
 
-def _compare_solve(g, o, tag, tol=None, x=None):
+def _compare_solve(g, o, tag, tol=None, x=None, solve=None):
     """Discrete history identical, statistics within rounding, trajectories within FUZZ_TOL of each other -- or, where a problem amplifies
     rounding differences beyond that (x = the long-double arbiter of the same problem), the HIP path no further from the arbiter than
     the double oracle is: |hip - x| <= 4 |oracle - x| + FUZZ_TOL (both double programs miss the extended-precision run by the same
     amount; round 3 kept a list of such cases at 1e-7, tests/probes/fuzz_case_probe.py shows who is far)."""
     tol = FUZZ_TOL if tol is None else tol
+    solve = solve or (lambda b: b.newton_solve(init=True, game_id0=7))         # (tests/ibr_family.py: the IBR solve under the same rule)
     sx, same = None, None
-    sg, so = g.newton_solve(init=True, game_id0=7), o.newton_solve(init=True, game_id0=7)
+    sg, so = solve(g), solve(o)
     # Round 6: a game on which the two double programs end with different STATUSES is accepted only when the game has DIVERGED: the arbiter's
     # own iterate (long double, same algorithm, same inputs) is non-finite or beyond 1e6 (the problems start from x0 = O(1)).  That is the one game of seeds 400040 / 400059 /
     # 400074 -- iterates 7e7 ... 1e11 -> 1e54 -> 1e186, Newton directions of 1e54 ... inf (profiles/r06_dense_gap_seed_400040.txt) -- on which the
@@ -105,7 +106,7 @@ def _compare_solve(g, o, tag, tol=None, x=None):
     noise = np.zeros(len(sg), bool)
     if not np.array_equal(sg["status"], so["status"]):
         assert x is not None, (tag, "status", sg["status"], so["status"])
-        sx = x.newton_solve(init=True, game_id0=7)
+        sx = solve(x)
         zx_ = x.get_traj(0)
         for game in np.nonzero(sg["status"] != so["status"])[0]:
             diverged = (not np.isfinite(zx_[game]).all()) or np.abs(zx_[game]).max() > 1e6
@@ -121,7 +122,7 @@ def _compare_solve(g, o, tag, tol=None, x=None):
         scale = max(1.0, np.abs(zo[ok]).max())
         err = np.abs(zg[ok] - zo[ok]).max()
         if err > tol * scale and x is not None:
-            sx = x.newton_solve(init=True, game_id0=7) if sx is None else sx
+            sx = solve(x) if sx is None else sx
             same = np.all([sx[f] == so[f] for f in ("status", "outer_iters", "newton_iters", "ls_failures")], axis=0) & ok
             zx = x.get_traj(0)
             eg, eo = np.abs(zg[same] - zx[same]).max(initial=0.0), np.abs(zo[same] - zx[same]).max(initial=0.0)
@@ -139,7 +140,7 @@ def _compare_solve(g, o, tag, tol=None, x=None):
             else:
                 # (the violation maxima of a non-converged last record are steep functions of the iterate -- penalties of 1e3 and more -- and
                 # can part by more than 1e-6 on trajectories that agree to the tolerance: seed 200041, opt_vio 13.49541868 against 13.49539232)
-                sx = x.newton_solve(init=True, game_id0=7) if sx is None else sx
+                sx = solve(x) if sx is None else sx
                 if tag[:4] not in ARBITER_CONSULTED: ARBITER_CONSULTED.append(tag[:4])
                 # a problem that went through the arbiter for its trajectories (both double programs amplify rounding beyond the
                 # tolerance): the statistics of the last record are functions of those trajectories and follow the same rule -- the HIP
