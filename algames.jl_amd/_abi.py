@@ -28,6 +28,10 @@ ALG_PLANT_RK2, ALG_PLANT_RK4 = 0, 1    # alg_mpc_set_plant: the plant's integrat
 PLANT_INTEGRATORS = ("rk2", "rk4")
 ALG_KKT_RHS_USER, ALG_KKT_RHS_X0, ALG_KKT_RHS_XF = 0, 1, 2    # alg_kkt_solve: the right-hand sides' kind
 SCEN_KINDS = ("collision_radius", "collision_cost", "control_bound", "state_bound", "wall", "circle", "wall3d", "cylinder")
+# kinds of constraint rows, in the order of the knot layout (alg_get_con_values, alg_mpc_get_con: the columns of worst / first)
+(ALG_CON_COLLISION, ALG_CON_CONTROL, ALG_CON_STATE, ALG_CON_WALL, ALG_CON_CIRCLE, ALG_CON_WALL3D, ALG_CON_CYLINDER) = range(7)
+ALG_CON_KINDS = 7
+CON_KINDS = ("collision", "control", "state", "wall", "circle", "wall3d", "cylinder")
 
 
 class alg_desc(C.Structure):
@@ -173,13 +177,19 @@ SIGNATURES = {
     "mpc_set_cost_log": (C.c_int, [_P, C.c_int32]),
     "mpc_get_cost_log": (C.c_int, [_P, _I]),
     "mpc_get_cost": (C.c_int, [_P, C.c_int32, _D, _D, _I]),
+    "get_con_values": (C.c_int, [_P, C.c_int32, _D]),
+    "con_knot_len": (C.c_int, [_P, _I]),
+    "mpc_set_con_log": (C.c_int, [_P, C.c_int32]),
+    "mpc_get_con_log": (C.c_int, [_P, _I]),
+    "mpc_get_con": (C.c_int, [_P, C.c_int32, _D, _D, _I, _I]),
 }
 # Entry points a backend may lack (the CPU oracle has no per-game scenario data): bound when present; calling one that is absent
 # raises AlgamesError naming the backend.
 OPTIONAL = frozenset({"scenario_data_len", "set_scenario_data", "get_scenario_data", "set_scenario_kernels", "get_scenario_kernels",
                       "mpc_set_schedule", "mpc_get_schedule", "mpc_solve_log", "mpc_set_plant", "mpc_get_plant", "mpc_plant_advance", "kkt_solve",
                       "set_history_profiles", "get_history_profiles", "get_history_vio",
-                      "get_cost", "mpc_set_cost_log", "mpc_get_cost_log", "mpc_get_cost"})
+                      "get_cost", "mpc_set_cost_log", "mpc_get_cost_log", "mpc_get_cost",
+                      "get_con_values", "con_knot_len", "mpc_set_con_log", "mpc_get_con_log", "mpc_get_con"})
 
 
 class AlgamesError(RuntimeError):
@@ -592,6 +602,23 @@ class Batch:
         self.lib.check(self.lib.get_cost(self.h, int(which), _dptr(total), _dptr(st)))
         return (total, st) if stage else total
 
+    def get_con_values(self, which=ALG_TRAJ_PD):
+        """The constraint values of the plan, read-only (alg_get_con_values): (B, con_len) in the ABI's constraint layout, the rows of
+        dual_penalty_update's vals -- c <= 0 feasible, -inf for a row of an infinite bound, 0 for an inert row -- without its dual and
+        penalty update.  which: ALG_TRAJ_PD or ALG_TRAJ_TRIAL.  Changes nothing on the handle; a backend without the entry point (the CPU
+        oracle) raises AlgamesError."""
+        if isinstance(which, bool) or not isinstance(which, (int, np.integer)) or int(which) not in (ALG_TRAJ_PD, ALG_TRAJ_TRIAL):
+            raise ValueError(f"get_con_values: which must be ALG_TRAJ_PD (0) or ALG_TRAJ_TRIAL (1), got {which!r}")
+        vals = np.empty((self.B, self.con_len))
+        self.lib.check(self.lib.get_con_values(self.h, int(which), _dptr(vals)))
+        return vals
+
+    def con_knot_len(self):
+        """K1, the constraint rows of one step (alg_con_knot_len): con_len = (N - 1) K1"""
+        v = C.c_int32()
+        self.lib.check(self.lib.con_knot_len(self.h, C.byref(v)))
+        return v.value
+
     def newton_direction(self, reg=0.0):
         delta = np.empty((self.B, self.S)); st = np.empty(self.B, dtype=np.int32)
         self.lib.check(self.lib.newton_direction(self.h, reg, _dptr(delta), _iptr(st)))
@@ -800,6 +827,36 @@ class Batch:
         stage = np.empty((k, self.B, self.p, 3)); total = np.empty((self.B, self.p, 3))
         self.lib.check(self.lib.mpc_get_cost(self.h, k, _dptr(stage), _dptr(total), C.byref(v)))
         return stage, total
+
+    def mpc_set_con_log(self, on=True):
+        """Closed-loop constraint log of mpc_solve / mpc_solve_log (alg_mpc_set_con_log; off by default): with it on the loop also leaves
+        the constraint values of every plant knot on the device (mpc_get_con).  A backend without it (the CPU oracle) raises AlgamesError."""
+        if not isinstance(on, (bool, int, np.integer)):
+            raise ValueError(f"mpc_set_con_log: on must be a bool, got {on!r}")
+        self.lib.check(self.lib.mpc_set_con_log(self.h, int(bool(on))))
+
+    def mpc_get_con_log(self):
+        v = C.c_int32()
+        self.lib.check(self.lib.mpc_get_con_log(self.h, C.byref(v)))
+        return bool(v.value)
+
+    def mpc_get_con(self, max_knots=None):
+        """The constraint log of the most recent mpc_solve / mpc_solve_log (alg_mpc_get_con; waits for the stream): (vals (k, B, K1), worst
+        (B, 7), first (B, 7) int32), k = min(max_knots, knots).  vals[q, g] are the rows of one step in the knot layout (con_knot_len): the
+        control-bound rows on controls[q], every other row on states[q + 1], with the schedule rows the knot's solve used.  worst: the
+        maximum of every ALG_CON_* kind's rows over ALL knots (-inf: kind not added, NaN: a row is NaN); first: the first knot with a row
+        that is not <= 0, -1 if none.  (None, None, None) while there is no log: log off, no loop yet, or invalidated by an adder, set_lqr,
+        set_scenario_data or mpc_set_schedule."""
+        if max_knots is not None and (isinstance(max_knots, bool) or not isinstance(max_knots, (int, np.integer)) or max_knots < 0):
+            raise ValueError(f"mpc_get_con: max_knots must be a non-negative integer or None, got {max_knots!r}")
+        v = C.c_int32()
+        self.lib.check(self.lib.mpc_get_con(self.h, 0, None, None, None, C.byref(v)))
+        if v.value == 0:
+            return None, None, None
+        k = v.value if max_knots is None else min(int(max_knots), v.value)
+        vals = np.empty((k, self.B, self.con_knot_len())); worst = np.empty((self.B, ALG_CON_KINDS)); first = np.empty((self.B, ALG_CON_KINDS), dtype=np.int32)
+        self.lib.check(self.lib.mpc_get_con(self.h, k, _dptr(vals), _dptr(worst), _iptr(first), C.byref(v)))
+        return vals, worst, first
 
     # ---- schedules of the fused loop (alg_mpc_set_schedule) ----------------------------------
     def _sched_kind(self, kind):

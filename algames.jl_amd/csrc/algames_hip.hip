@@ -263,7 +263,14 @@ struct Handle {
     double* d_cost = nullptr;
     size_t cost_cap = 0;          // plant knots the buffer holds
     int cost_knots = 0;           // plant knots of the loop the buffer belongs to; 0 = none / invalidated (adders, alg_set_lqr, alg_set_scenario_data, alg_mpc_set_schedule)
+    // closed-loop constraint log (alg_mpc_set_con_log): [vals (knots x B x K1) | worst (B x 7 doubles) | first (B x 7 int32)], the same life cycle
+    bool con_log = false;
+    double* d_con = nullptr;
+    size_t con_cap = 0;           // doubles of vals the buffer holds
+    int con_knots = 0, con_k1 = 0;   // plant knots and rows per knot of the loop the buffer belongs to; con_knots = 0: none / invalidated
 };
+// doubles of the constraint log's summary behind vals: worst, then first (int32, rounded up to whole doubles)
+size_t con_summary_len(int B) { return (size_t)B * ALG_CON_KINDS + ((size_t)B * ALG_CON_KINDS + 1) / 2; }
 
 constexpr size_t GUARD = 4096;     // guard zone behind every device buffer (checked by alg_debug_check_guards)
 template <class T>
@@ -536,7 +543,7 @@ void scen_image(const Handle* hd, double* blk) {
 int scen_commit(Handle* hd) {
     Params& p = hd->pr;
     if (!hd->keep_sched) sched_drop_all(hd);       // an adder drops every schedule, as it drops per-game data
-    hd->cost_knots = 0;                            // ... and the cost log no longer belongs to the handle's data
+    hd->cost_knots = 0; hd->con_knots = 0;                            // ... and the cost and constraint logs no longer belong to the handle's data
     hd->scen_kinds = 0;
     p.scen = hd->d_scen; p.scen_stride = 0;
     if (p.ext == 2) p.ext = 0;
@@ -741,7 +748,7 @@ int set_scenario_data(alg_handle* h, const char* who, int32_t kind, const double
     scen_image(H, img.data());
     int rc = use_device(H); if (rc) return rc;
     if (!data) {                  // back to the shared values
-        H->cost_knots = 0;
+        H->cost_knots = 0; H->con_knots = 0;
         if (!((H->scen_kinds >> kind) & 1u)) return ALG_OK;
         H->scen_kinds &= ~(1u << kind);
         if (!H->scen_kinds) { p.scen = H->d_scen; p.scen_stride = 0; if (p.ext == 2) p.ext = 0; return ALG_OK; }
@@ -773,7 +780,7 @@ int set_scenario_data(alg_handle* h, const char* who, int32_t kind, const double
     H->scen_kinds |= 1u << kind;
     p.scen = H->d_scen_games; p.scen_stride = (int)SS;
     if (stay_base) p.ext = 2;
-    H->cost_knots = 0;
+    H->cost_knots = 0; H->con_knots = 0;
     return ALG_OK;
 }
 
@@ -803,7 +810,22 @@ int mpc_solve_impl(const char* who, alg_handle* h, int32_t steps, int64_t game_i
             H->cost_cap = knots;
         }
     }
-    const size_t b_st = (states || clog) ? sizeof(double) * (knots + 1) * p.B * p.n : 0, b_uc = (controls || clog) ? sizeof(double) * knots * p.B * p.m : 0,
+    // the constraint log (alg_mpc_set_con_log): the same, in a buffer of its own
+    const bool klog = H->con_log;
+    const size_t k1 = (size_t)(p.con_len / (p.N - 1)), kvals = knots * (size_t)p.B * k1;
+    H->con_knots = 0;
+    if (klog) {
+        if (kvals + con_summary_len(p.B) > ((size_t)1 << 30) / sizeof(double)) return fail(ALG_ERR_ARG, std::string(who) + ": the constraint log of this run would exceed 1 GiB");
+        if (kvals > H->con_cap) {
+            if ((rc = sync(H))) return rc;
+            if (H->d_con) dfree(H, H->d_con);
+            H->d_con = nullptr; H->con_cap = 0;
+            if ((rc = dalloc(H, &H->d_con, kvals + con_summary_len(p.B), "closed-loop constraint log"))) return rc;
+            H->con_cap = kvals;
+        }
+    }
+    const bool dlog = clog || klog;               // the logs that keep states and controls on the device
+    const size_t b_st = (states || dlog) ? sizeof(double) * (knots + 1) * p.B * p.n : 0, b_uc = (controls || dlog) ? sizeof(double) * knots * p.B * p.m : 0,
                  b_gs = stats ? sizeof(alg_game_stats) * (size_t)steps * p.B : 0;
     static_assert(sizeof(alg_game_stats) % 8 == 0, "the stats log follows doubles in the scratch");
     if (b_st + b_uc + b_gs && (rc = ensure_scratch(H, b_st + b_uc + b_gs))) return rc;
@@ -814,7 +836,7 @@ int mpc_solve_impl(const char* who, alg_handle* h, int32_t steps, int64_t game_i
     bool scheduled = false;
     for (int k = 0; k < ALG_SCHED_MAX_KINDS; k++) scheduled |= H->sched[k].rows > 0;
     // the sibling kernels are the loop with per-step phases: a schedule, a disturbance, a log or a plant takes them
-    if (!scheduled && !H->dist.rows && !controls && !stats && !planted && !clog) rc = launch_mpc_loop(H, (int)steps, (uint64_t)game_id0, d_states);
+    if (!scheduled && !H->dist.rows && !controls && !stats && !planted && !dlog) rc = launch_mpc_loop(H, (int)steps, (uint64_t)game_id0, d_states);
     else rc = launch_mpc_loop_sched(H, (int)steps, (uint64_t)game_id0, d_states, d_controls, d_stats);
     if (rc) return rc;
     if (clog) {
@@ -829,6 +851,21 @@ int mpc_solve_impl(const char* who, alg_handle* h, int32_t steps, int64_t game_i
         if (cc.rows) { ca.cc = cc.d_data; ca.cc_rows = cc.rows; }
         LAUNCH(k_closed_loop_cost, H->pr, ca);
         H->cost_knots = (int)knots;
+    }
+    if (klog) {
+        // behind the loop (and the cost kernel) on the same stream: [vals | worst | first], rows of the schedules the loop read
+        ConLoopArgs ka; std::memset(&ka, 0, sizeof(ka));
+        ka.states = d_states; ka.controls = d_controls;
+        ka.vals = H->d_con; ka.worst = H->d_con + kvals; ka.first = (int*)(ka.worst + (size_t)p.B * ALG_CON_KINDS);
+        ka.knots = (int)knots; ka.hold = H->plant.hold;
+        static const int kind_of[ALG_CON_KINDS] = {ALG_SCEN_COLLISION_RADIUS, ALG_SCEN_CONTROL_BOUND, ALG_SCEN_STATE_BOUND, ALG_SCEN_WALL,
+                                                   ALG_SCEN_CIRCLE, ALG_SCEN_WALL3D, ALG_SCEN_CYLINDER};
+        for (int c = 0; c < ALG_CON_KINDS; c++) {
+            const Handle::Sched& sc = H->sched[sched_slot(kind_of[c])];
+            if (sc.rows) { ka.sched[c] = sc.d_data; ka.rows[c] = sc.rows; }
+        }
+        LAUNCH(k_closed_loop_con, H->pr, ka);
+        H->con_knots = (int)knots; H->con_k1 = (int)k1;
     }
     // the loop leaves the row its last step used in the games' blocks: the host mirror of the scenario blocks follows (what the step-wise
     // alg_set_scenario_data calls would have left; the LQR blocks have no host mirror)
@@ -850,7 +887,7 @@ int mpc_solve_impl(const char* who, alg_handle* h, int32_t steps, int64_t game_i
 // The plant disturbance (ALG_SCHED_DISTURBANCE): rows x B x n, needs nothing of the handle but its sizes
 int set_disturbance(Handle* hd, int32_t rows, const double* data) {
     int rc = use_device(hd); if (rc) return rc;
-    if (!data) { sched_drop(hd, hd->dist); hd->cost_knots = 0; return ALG_OK; }
+    if (!data) { sched_drop(hd, hd->dist); hd->cost_knots = 0; hd->con_knots = 0; return ALG_OK; }
     if (rows < 1) return fail(ALG_ERR_ARG, "alg_mpc_set_schedule: rows must be >= 1");
     const Params& p = hd->pr;
     const size_t per_row = (size_t)p.B * p.n, cnt = (size_t)rows * per_row;
@@ -862,7 +899,7 @@ int set_disturbance(Handle* hd, int32_t rows, const double* data) {
     if ((rc = h2d(hd, sc.d_data, data, sizeof(double) * cnt))) { dfree(hd, sc.d_data); return rc; }
     sched_drop(hd, hd->dist);
     hd->dist = std::move(sc);
-    hd->cost_knots = 0;
+    hd->cost_knots = 0; hd->con_knots = 0;
     return ALG_OK;
 }
 
@@ -1018,7 +1055,7 @@ int alg_set_lqr(alg_handle* h, const double* Qd, const double* Rd, const double*
     if ((rc = sync(H))) return rc;
     p.lqr_per_game = per_game ? 1 : 0; p.lqr_stride = per_game ? blk : 0;
     H->lqr_set = true;
-    H->cost_knots = 0;
+    H->cost_knots = 0; H->con_knots = 0;
     sched_drop(H, sched_slot(ALG_SCHED_LQR_TARGET));   // the target schedule goes with the data it was set against
     return ALG_OK;
 }
@@ -1307,6 +1344,24 @@ int alg_get_cost(alg_handle* h, int32_t which, double* total, double* stage) {
     if (total && (rc = d2h(H, total, d, b_tot))) return rc;
     if (stage && (rc = d2h(H, stage, d + b_tot, b_stg))) return rc;
     return ALG_OK;
+}
+
+// Constraint values of the plan (k_con_values): B x con_len in the inspection scratch, one launch, one copy back
+int alg_get_con_values(alg_handle* h, int32_t which, double* vals) {
+    NEED_HANDLE("alg_get_con_values");
+    if (which != ALG_TRAJ_PD && which != ALG_TRAJ_TRIAL) return fail(ALG_ERR_ARG, "alg_get_con_values: which must be ALG_TRAJ_PD or ALG_TRAJ_TRIAL");
+    if (!vals) return fail(ALG_ERR_ARG, "alg_get_con_values: vals is null");
+    if (!H->x0_set) return fail(ALG_ERR_STATE, "alg_get_con_values: x0 not set");
+    int rc = use_device(H); if (rc) return rc;
+    const Params& p = H->pr;
+    const size_t bytes = sizeof(double) * (size_t)p.B * p.con_len;
+    if ((rc = ensure_scratch(H, bytes))) return rc;
+    LAUNCH(k_con_values, H->pr, (int)which, (double*)H->d_scratch);
+    return d2h(H, vals, H->d_scratch, bytes);
+}
+int alg_con_knot_len(alg_handle* h, int32_t* len) {
+    if (!h || !len) return fail(ALG_ERR_ARG, "alg_con_knot_len: null argument");
+    *len = H->pr.con_len / (H->pr.N - 1); return ALG_OK;
 }
 
 int alg_newton_direction(alg_handle* h, double reg, double* delta, int32_t* status) {
@@ -1622,6 +1677,39 @@ int alg_mpc_get_cost(alg_handle* h, int32_t max_knots, double* stage, double* to
     *knots_out = H->cost_knots;
     return ALG_OK;
 }
+// The closed-loop constraint log of the fused loop (include/algames_hip.h): mpc_solve_impl fills it, k_closed_loop_con evaluates it
+int alg_mpc_set_con_log(alg_handle* h, int32_t on) {
+    NEED_HANDLE("alg_mpc_set_con_log");
+    if (!on && H->d_con) {
+        int rc = use_device(H); if (rc) return rc;
+        if ((rc = sync(H))) return rc;             // a loop that writes the log may still run
+        dfree(H, H->d_con);
+        H->d_con = nullptr; H->con_cap = 0;
+    }
+    if (!on) H->con_knots = 0;
+    H->con_log = on != 0;
+    return ALG_OK;
+}
+int alg_mpc_get_con_log(alg_handle* h, int32_t* on) {
+    if (!h || !on) return fail(ALG_ERR_ARG, "alg_mpc_get_con_log: null argument");
+    *on = H->con_log ? 1 : 0; return ALG_OK;
+}
+int alg_mpc_get_con(alg_handle* h, int32_t max_knots, double* vals, double* worst, int32_t* first, int32_t* knots_out) {
+    if (!h || !knots_out) return fail(ALG_ERR_ARG, "alg_mpc_get_con: null argument");
+    if (max_knots < 0) return fail(ALG_ERR_ARG, "alg_mpc_get_con: max_knots must be >= 0");
+    *knots_out = 0;
+    if (!H->con_log || !H->con_knots) return ALG_OK;
+    int rc = use_device(H); if (rc) return rc;
+    const Params& p = H->pr;
+    const size_t per = (size_t)p.B * H->con_k1, rows = (size_t)std::min<int>(max_knots, H->con_knots), nsum = (size_t)p.B * ALG_CON_KINDS;
+    const double* d_worst = H->d_con + (size_t)H->con_knots * per;
+    if (vals && rows && (rc = d2h(H, vals, H->d_con, sizeof(double) * rows * per))) return rc;
+    if (worst && (rc = d2h(H, worst, d_worst, sizeof(double) * nsum))) return rc;
+    if (first && (rc = d2h(H, first, d_worst + nsum, sizeof(int32_t) * nsum))) return rc;
+    if ((rc = sync(H))) return rc;
+    *knots_out = H->con_knots;
+    return ALG_OK;
+}
 // Schedules of alg_mpc_solve: per game and per MPC step values of one kind (include/algames_hip.h)
 int alg_mpc_set_schedule(alg_handle* h, int32_t kind, int32_t rows, const double* data) {
     static const char* who = "alg_mpc_set_schedule";
@@ -1631,7 +1719,7 @@ int alg_mpc_set_schedule(alg_handle* h, int32_t kind, int32_t rows, const double
     if (!target && !scen_kind_ok(kind)) return fail(ALG_ERR_ARG, "alg_mpc_set_schedule: unknown kind (an ALG_SCEN_* value, ALG_SCHED_LQR_TARGET or ALG_SCHED_DISTURBANCE)");
     const int slot = sched_slot(kind);
     int rc = use_device(H); if (rc) return rc;
-    if (!data) { sched_drop(H, slot); H->cost_knots = 0; return ALG_OK; }
+    if (!data) { sched_drop(H, slot); H->cost_knots = 0; H->con_knots = 0; return ALG_OK; }
     if (rows < 1) return fail(ALG_ERR_ARG, "alg_mpc_set_schedule: rows must be >= 1");
     const Params& p = H->pr;
     std::vector<int> map;
@@ -1674,7 +1762,7 @@ int alg_mpc_set_schedule(alg_handle* h, int32_t kind, int32_t rows, const double
     sc.data.assign(data, data + cnt); sc.map = map;
     sched_drop(H, slot);
     H->sched[slot] = std::move(sc);
-    H->cost_knots = 0;
+    H->cost_knots = 0; H->con_knots = 0;
     return ALG_OK;
 }
 int alg_mpc_get_schedule(alg_handle* h, int32_t kind, int32_t* rows) {

@@ -592,6 +592,8 @@ __global__ void __launch_bounds__(WAVE, C::WPE) k_kkt_solve(Params pr_arg, doubl
 
 // Players' costs of a plan and of a closed-loop run (k_player_cost, k_closed_loop_cost)
 #include "algames_cost.hpp"
+// Constraint values of a plan and of a closed-loop run, row by row (k_con_values, k_closed_loop_con)
+#include "algames_con.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // Instantiation lists: X(model, p, d, ext)
@@ -767,11 +769,14 @@ __global__ void __launch_bounds__(WAVE, C::WPE) k_kkt_solve(Params pr_arg, doubl
 #define ALG_DECLARE_SCHED(M, P, D, E) ALG_INSTANTIATE_SCHED(extern template, M, P, D, E)
 #define ALG_DEFINE_SCHED_MW(M, P, D, E, W) ALG_INSTANTIATE_SCHED_MW(template, M, P, D, E, W)
 // The step-wise plant knot (k_mpc_plant_advance): one per one-wavefront configuration (ALG_CFGS_ONE), in a unit of their own -- with the two
-// cost kernels of algames_cost.hpp (k_player_cost, k_closed_loop_cost: one wavefront per game for every handle, like the plant knot)
+// cost kernels of algames_cost.hpp (k_player_cost, k_closed_loop_cost) and the two constraint kernels of algames_con.hpp (k_con_values,
+// k_closed_loop_con): one wavefront per game for every handle, like the plant knot
 #define ALG_INSTANTIATE_PLANT(PREFIX, M, P, D, E)                                                                          \
     PREFIX __global__ void k_mpc_plant_advance<Cfg<M, P, D, E>>(Params, int, MpcPlant);                                    \
     PREFIX __global__ void k_player_cost<Cfg<M, P, D, E>>(Params, int, double*, double*);                                  \
-    PREFIX __global__ void k_closed_loop_cost<Cfg<M, P, D, E>>(Params, CostLoopArgs);
+    PREFIX __global__ void k_closed_loop_cost<Cfg<M, P, D, E>>(Params, CostLoopArgs);                                      \
+    PREFIX __global__ void k_con_values<Cfg<M, P, D, E>>(Params, int, double*);                                            \
+    PREFIX __global__ void k_closed_loop_con<Cfg<M, P, D, E>>(Params, ConLoopArgs);
 #define ALG_DEFINE_PLANT(M, P, D, E) ALG_INSTANTIATE_PLANT(template, M, P, D, E)
 #define ALG_DECLARE_PLANT(M, P, D, E) ALG_INSTANTIATE_PLANT(extern template, M, P, D, E)
 #define ALG_DECLARE_SCHED_MW(M, P, D, E, W) ALG_INSTANTIATE_SCHED_MW(extern template, M, P, D, E, W)

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import (ALG_MODEL_BICYCLE, ALG_MODEL_DOUBLE_INTEGRATOR, ALG_MODEL_QUADROTOR, ALG_MODEL_UNICYCLE, ALG_TRAJ_PD, ALG_TRAJ_TRIAL,
-                   ALG_TRAJ_DELTA, ALG_SCEN_COLLISION_COST, ALG_SCHED_LQR_TARGET, ALG_SCHED_DISTURBANCE, AlgamesError, Batch, CLib, Plant)
+                   ALG_TRAJ_DELTA, ALG_SCEN_COLLISION_COST, ALG_SCHED_LQR_TARGET, ALG_SCHED_DISTURBANCE, ALG_CON_KINDS, AlgamesError, Batch, CLib, Plant)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.environ.get("ALGAMES_HIP_LIB", os.path.join(_HERE, "lib", "libalgames_hip.so"))
@@ -1128,6 +1128,136 @@ def _cost_numbers(prob, sched, t):
     return Q, R, xf, uf, rad, mu
 
 
+def constraint_values(prob, which="pd"):
+    """The constraint values of the plan, read-only, evaluated on the device (alg_get_con_values): (B, con_len) in the ABI's constraint
+    layout -- evaluate!(game_con, traj) (constraints_methods.jl:329-379) without the dual and penalty update; c <= 0 is feasible, a row of
+    an infinite bound reports -inf, an inert row 0.  which: "pd" (prob.pdtraj) or "trial" (prob.pdtraj_trial)."""
+    code = {"pd": ALG_TRAJ_PD, "trial": ALG_TRAJ_TRIAL}.get(which, which) if isinstance(which, str) else which
+    if isinstance(code, str):
+        raise ValueError(f"constraint_values: which must be 'pd' or 'trial', got {which!r}")
+    return prob.batch.get_con_values(code)
+
+
+def _con_tables(prob):
+    """What the constraint rows of a knot are built from, host side: {ALG_SCEN_* kind: (B, len) numbers in the caller's order} of every
+    constraint kind the problem carries (scenario_data's arrays: a schedule row of the kind has the same layout) and the structure the
+    handle keeps -- pair mask (p, p), spherical, per-player masks (p, entries) of the four tables, cylinder axes."""
+    from ._abi import ALG_SCEN_WALL, ALG_SCEN_CIRCLE, ALG_SCEN_WALL3D, ALG_SCEN_CYLINDER
+    b = prob.batch
+    cons = prob.game_cons or [prob.game_con] * b.B
+    gc, p = cons[0], b.p
+    nums = scenario_data(cons, None, every_kind=True)
+    pairs = np.zeros((p, p), dtype=bool)
+    if gc.collision_radius is not None:
+        pairs[:] = ~np.eye(p, dtype=bool)
+    for (i, j) in gc.collision_pairs:
+        pairs[i - 1, j - 1] = True
+    masks = {}
+    for kind, rows_fn, own, shared in ((ALG_SCEN_WALL, _wall_rows, "player_walls", "walls"), (ALG_SCEN_CIRCLE, _circle_rows, "player_circles", "circles"),
+                                       (ALG_SCEN_WALL3D, _wall3_rows, "player_walls3d", "walls3d"), (ALG_SCEN_CYLINDER, _cyl_rows, "player_cylinders", "cylinders")):
+        if getattr(gc, shared):
+            masks[kind] = np.ones((p, len(rows_fn(getattr(gc, shared)))), dtype=bool)
+        elif getattr(gc, own):
+            rows, owners = _player_table({i: rows_fn(v) for i, v in getattr(gc, own).items()})
+            masks[kind] = np.zeros((p, len(rows)), dtype=bool)
+            for e, own_e in enumerate(owners):
+                for (i, _) in own_e:
+                    masks[kind][i - 1, e] = True
+    axes = None
+    if gc.cylinders:
+        axes = np.array([c.v for c in gc.cylinders])
+    elif gc.player_cylinders:
+        axes = np.array([int(r[3]) for r in _player_table({i: _cyl_rows(v) for i, v in gc.player_cylinders.items()})[0]])
+    return dict(nums=nums, pairs=pairs, spherical=bool(gc.spherical), masks=masks, axes=axes)
+
+
+def _con_knot(b, tab, nums, x, u):
+    """The K1 constraint rows of one step in numpy (alg_get_con_values' knot layout): x (B, n) the state the step reaches, u (B, m) its
+    control in the stored player-major order, nums {kind: (B, len)} the numbers in force.  Returns (vals (B, K1), kind of every row (K1,):
+    an ALG_CON_* value, -1 for the rows of a base block that was not added)."""
+    from ._abi import (ALG_SCEN_COLLISION_RADIUS, ALG_SCEN_CONTROL_BOUND, ALG_SCEN_STATE_BOUND, ALG_SCEN_WALL, ALG_SCEN_CIRCLE,
+                       ALG_SCEN_WALL3D, ALG_SCEN_CYLINDER)
+    B, p, n, m = x.shape[0], b.p, b.n, b.m
+    pos = lambda i, a: x[:, a * p + i]                              # pz_i[a] = a p + i
+    out, kinds = [], []
+    for i in range(p):
+        for j in range(p):
+            if j == i:
+                continue
+            if ALG_SCEN_COLLISION_RADIUS in nums and tab["pairs"][i, j]:
+                R = nums[ALG_SCEN_COLLISION_RADIUS].reshape(B, p, p)[:, i, j]
+                d2 = sum((pos(i, a) - pos(j, a)) ** 2 for a in range(3 if tab["spherical"] else 2))
+                out.append(R * R - d2)
+            else:
+                out.append(np.zeros(B))
+            kinds.append(0 if ALG_SCEN_COLLISION_RADIUS in nums else -1)
+    uj = u.reshape(B, p, b.mi).transpose(0, 2, 1).reshape(B, m)     # joint order c = a p + i
+    if ALG_SCEN_CONTROL_BOUND in nums:
+        bd = nums[ALG_SCEN_CONTROL_BOUND]
+        out += list((uj - bd[:, :m]).T) + list((bd[:, m:] - uj).T)
+        kinds += [1] * (2 * m)
+    else:
+        out += [np.zeros(B)] * (2 * m)
+        kinds += [-1] * (2 * m)
+    if ALG_SCEN_STATE_BOUND in nums:
+        sb = nums[ALG_SCEN_STATE_BOUND].reshape(B, 2, p, n)
+        for i in range(p):
+            out += list((x - sb[:, 0, i]).T) + list((sb[:, 1, i] - x).T)
+            kinds += [2] * (2 * n)
+    if ALG_SCEN_WALL in nums:
+        W = nums[ALG_SCEN_WALL].reshape(B, -1, 6)
+        for i in range(p):
+            for w in range(W.shape[1]):
+                x1, y1, x2, y2, xv, yv = W[:, w].T
+                px, py = pos(i, 0), pos(i, 1)
+                inside = ((px - x1) * (x2 - x1) + (py - y1) * (y2 - y1) > 0) & ((px - x2) * (x1 - x2) + (py - y2) * (y1 - y2) > 0)
+                out.append(np.where(inside & tab["masks"][ALG_SCEN_WALL][i, w], (px - x1) * xv + (py - y1) * yv, 0.0))
+                kinds.append(3)
+    if ALG_SCEN_CIRCLE in nums:
+        Cc = nums[ALG_SCEN_CIRCLE].reshape(B, -1, 3)
+        for i in range(p):
+            for c in range(Cc.shape[1]):
+                v = Cc[:, c, 2] ** 2 - (pos(i, 0) - Cc[:, c, 0]) ** 2 - (pos(i, 1) - Cc[:, c, 1]) ** 2
+                out.append(np.where(tab["masks"][ALG_SCEN_CIRCLE][i, c], v, 0.0))
+                kinds.append(4)
+    if ALG_SCEN_WALL3D in nums:
+        W = nums[ALG_SCEN_WALL3D].reshape(B, -1, 4, 3)
+        for i in range(p):
+            q = np.stack([pos(i, 0), pos(i, 1), pos(i, 2)], axis=1)
+            for w in range(W.shape[1]):
+                p1, p2, p3, v = (W[:, w, f] for f in range(4))
+                dot = lambda a, e, c: np.sum((q - a) * (e - c), axis=1)
+                inside = (dot(p1, p2, p1) > 0) & (dot(p2, p1, p2) > 0) & (dot(p3, p2, p3) > 0) & (dot(p2, p3, p2) > 0)
+                out.append(np.where(inside & tab["masks"][ALG_SCEN_WALL3D][i, w], np.sum((q - p1) * v, axis=1), 0.0))
+                kinds.append(5)
+    if ALG_SCEN_CYLINDER in nums:
+        Y = nums[ALG_SCEN_CYLINDER].reshape(B, -1, 5)
+        for i in range(p):
+            q = np.stack([pos(i, 0), pos(i, 1), pos(i, 2)], axis=1)
+            for c in range(Y.shape[1]):
+                t0 = q - Y[:, c, :3]
+                ta = t0[:, tab["axes"][c]]
+                v = Y[:, c, 4] ** 2 - np.sum(t0 ** 2, axis=1) + ta ** 2
+                out.append(np.where((ta > 0) & (ta < Y[:, c, 3]) & tab["masks"][ALG_SCEN_CYLINDER][i, c], v, 0.0))
+                kinds.append(6)
+    return np.stack(out, axis=1), np.array(kinds)
+
+
+def _con_summary(con, kinds):
+    """worst (B, 7) and first (B, 7) of a constraint log con (knots, B, K1): alg_mpc_get_con's summary"""
+    B = con.shape[1]
+    worst = np.full((B, ALG_CON_KINDS), -np.inf); first = np.full((B, ALG_CON_KINDS), -1, dtype=np.int32)
+    for c in range(ALG_CON_KINDS):
+        v = con[:, :, kinds == c]
+        if v.shape[2] == 0:
+            continue
+        worst[:, c] = v.max(axis=(0, 2)) + 0.0                      # (a NaN propagates; + 0.0: -0 reads +0)
+        bad = ~(v <= 0.0)
+        hit = bad.any(axis=2)
+        first[:, c] = np.where(hit.any(axis=0), hit.argmax(axis=0), -1)
+    return worst, first
+
+
 def dynamics_violation(prob):
     return prob.batch.record()["dyn_vio"]
 
@@ -1287,7 +1417,11 @@ class MpcRollout:
     control every knot held, player-major --, stats (steps, B) of game_stats_dtype -- every step's solve as get_stats reports it --, and the
     totals newton_iters (B,), converged (B,), which gain every solve once.  With costs=True also stage_cost (knots, B, p, 3) -- the running
     cost dt l_i(states[q], controls[q]) of every knot and player in the components [state, control, collision] of player_costs, taken with
-    the schedule rows the knot's solve used -- and cost (B, p, 3), its sum over the knots (no terminal term); None otherwise."""
+    the schedule rows the knot's solve used -- and cost (B, p, 3), its sum over the knots (no terminal term); None otherwise.  With
+    constraints=True also con (knots, B, K1) -- the constraint rows of every knot in the knot layout of alg_get_con_values: the control-bound
+    rows on controls[q], every other row on states[q + 1], with the schedule rows the knot's solve used --, con_worst (B, 7) -- the maximum
+    of every ALG_CON_* kind's rows over the run, -inf for a kind that was not added -- and con_first (B, 7) int32 -- the first knot with a
+    row that is not <= 0, -1 if none; None otherwise."""
     states: np.ndarray
     controls: np.ndarray
     stats: np.ndarray
@@ -1295,9 +1429,12 @@ class MpcRollout:
     converged: np.ndarray
     stage_cost: np.ndarray = None
     cost: np.ndarray = None
+    con: np.ndarray = None
+    con_worst: np.ndarray = None
+    con_first: np.ndarray = None
 
 
-def mpc_rollout(prob, steps=None, schedule=None, disturbance=None, fused=True, plant=None, costs=False):
+def mpc_rollout(prob, steps=None, schedule=None, disturbance=None, fused=True, plant=None, costs=False, constraints=False):
     """The receding-horizon loop as a closed-loop simulation: mpc_solve's loop with every step observable and a disturbed plant.  Returns
     an MpcRollout.  steps=None takes prob.opts.mpc_horizon.
 
@@ -1312,8 +1449,12 @@ def mpc_rollout(prob, steps=None, schedule=None, disturbance=None, fused=True, p
     without a plant), x0 read back, set_x0(x0 + w_q).
     costs=True: what the run cost each player (MpcRollout.stage_cost, .cost).  fused=True takes them from the device's cost log
     (Batch.mpc_set_cost_log, switched on for the call); fused=False evaluates the definition in numpy on the states and controls of the log
-    with the rows _apply_schedule_rows applied."""
+    with the rows _apply_schedule_rows applied.
+    constraints=True: did the run stay feasible (MpcRollout.con, .con_worst, .con_first)?  fused=True reads the device's constraint log
+    (Batch.mpc_set_con_log, switched on for the call); fused=False evaluates the definition in numpy the same way."""
     b = prob.batch
+    if not isinstance(constraints, (bool, np.bool_)):
+        raise ValueError(f"mpc_rollout: constraints must be a bool, got {constraints!r}")
     if steps is None:
         steps = prob.opts.mpc_horizon
     steps = int(steps)
@@ -1334,10 +1475,14 @@ def mpc_rollout(prob, steps=None, schedule=None, disturbance=None, fused=True, p
             up = sched + ([(ALG_SCHED_DISTURBANCE, w)] if w is not None else [])
             done = []
             log0 = b.mpc_get_cost_log() if costs else None
+            klog0 = b.mpc_get_con_log() if constraints else None
             stage_cost = cost = None
+            con = (None, None, None)
             try:
                 if costs:
                     b.mpc_set_cost_log(True)
+                if constraints:
+                    b.mpc_set_con_log(True)
                 for k, a in up:
                     b.mpc_set_schedule(k, a)
                     done.append(k)
@@ -1345,15 +1490,20 @@ def mpc_rollout(prob, steps=None, schedule=None, disturbance=None, fused=True, p
                 it, cv = b.mpc_totals()
                 if costs:
                     stage_cost, cost = b.mpc_get_cost()             # before the schedules go: dropping one invalidates the log
+                if constraints:
+                    con = b.mpc_get_con()
             finally:
                 for k in done:
                     b.mpc_set_schedule(k, None)
                 if costs and not log0:
                     b.mpc_set_cost_log(False)
-            return MpcRollout(states, controls, stats, it, cv, stage_cost, cost)
+                if constraints and not klog0:
+                    b.mpc_set_con_log(False)
+            return MpcRollout(states, controls, stats, it, cv, stage_cost, cost, *con)
         shift0, reset0 = prob.opts.shift, prob.opts.dual_reset
         n, m = b.n, b.m
-        states, controls, stats, stage_cost = [b.get_x0()], [], [], []
+        states, controls, stats, stage_cost, con = [b.get_x0()], [], [], [], []
+        tab = _con_tables(prob) if constraints else None
         stepwise_plant = plant is not None or not pl.is_default
         try:
             for t in range(steps):
@@ -1365,6 +1515,9 @@ def mpc_rollout(prob, steps=None, schedule=None, disturbance=None, fused=True, p
                 stats.append(b.get_stats())
                 z = b.get_traj()
                 nums = _cost_numbers(prob, sched, t) if costs else None
+                if constraints:                                     # the problem's numbers, row min(t, rows - 1) of a scheduled kind in their place
+                    knums = dict(tab["nums"])
+                    knums.update({k: a[min(t, a.shape[0] - 1)] for k, a in sched if k in knums})
                 for j in range(pl.hold):
                     q = t * pl.hold + j
                     controls.append(z[:, 2 * n + j * b.b:2 * n + j * b.b + m].copy())
@@ -1379,11 +1532,17 @@ def mpc_rollout(prob, steps=None, schedule=None, disturbance=None, fused=True, p
                         x1 = x1 + w[min(q, w.shape[0] - 1)]
                         b.set_x0(x1)
                     states.append(x1)
+                    if constraints:
+                        con.append(_con_knot(b, tab, knums, x1, controls[-1]))
             it, cv = b.mpc_totals()
         finally:
             prob.opts.shift, prob.opts.dual_reset = shift0, reset0
             prob._sync_options()
+        ro = MpcRollout(np.stack(states), np.stack(controls), np.stack(stats), it, cv)
         if costs:
-            stage_cost = np.stack(stage_cost)
-            return MpcRollout(np.stack(states), np.stack(controls), np.stack(stats), it, cv, stage_cost, stage_cost.sum(axis=0))
-        return MpcRollout(np.stack(states), np.stack(controls), np.stack(stats), it, cv)
+            ro.stage_cost = np.stack(stage_cost)
+            ro.cost = ro.stage_cost.sum(axis=0)
+        if constraints:
+            ro.con = np.stack([v for v, _ in con])
+            ro.con_worst, ro.con_first = _con_summary(ro.con, con[0][1])
+        return ro

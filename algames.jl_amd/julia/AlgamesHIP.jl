@@ -11,6 +11,7 @@
 #   mpc_solve!(bp, steps; schedule)                   receding-horizon loop of BASELINE config 5 (opts.shift / opts.dual_reset), with per-step values of targets / obstacles
 #   mpc_solve_log!(bp, steps; disturbance)            the same loop with the closed-loop log (controls and statistics of every step) and a plant disturbance
 #   player_costs(bp), set_mpc_cost_log!(bp, on), mpc_costs(bp)    what a plan / a closed-loop run costs each player, evaluated on the device
+#   constraint_values(bp), set_mpc_con_log!(bp, on), mpc_constraints(bp)    the constraint rows of a plan / a closed-loop run, read-only, evaluated on the device
 #   newton_solve!(probs::Vector{<:GameProblem})       convenience: build a handle, solve, release
 #   sp = ShardedGameProblem(probs; devices=0:7); newton_solve!(sp)     the batch split over several devices (one handle each)
 # After a solve every `prob.pdtraj`, the multipliers / penalties / values of every constraint (`conval.λ`, `.μ`, `.vals`,
@@ -637,16 +638,17 @@ function mpc_solve!(bp::BatchedGameProblem, steps::Integer; game_id0::Integer=0,
 end
 
 """
-    mpc_solve_log!(bp, steps; game_id0=0, schedule=nothing, disturbance=nothing, costs=false) -> (newton_iters, converged, states, controls, stats[, costs])
+    mpc_solve_log!(bp, steps; game_id0=0, schedule=nothing, disturbance=nothing, costs=false, constraints=false) -> (newton_iters, converged, states, controls, stats[, costs][, constraints])
 
 The loop of `mpc_solve!` with the closed-loop log (`alg_mpc_solve_log`): `controls` is m x B x steps (the joint control every advance
 applied, player-major), `stats` a B x steps matrix of `AlgGameStats` (every step's solve as `alg_get_stats` reports it).
 `schedule`: as for `mpc_solve!`.  `disturbance`: n x B x rows, finite -- after the advance of the step-th solve the state becomes
 x0 + slice min(step, rows); `states` holds the disturbed states.  It travels as one more schedule kind (`SCHED_DISTURBANCE`): uploaded
 and dropped again with the others.  `costs=true` switches the cost log on for the call (`set_mpc_cost_log!`) and appends `mpc_costs(bp)`,
-read before the schedules are dropped, to the result.
+read before the schedules are dropped, to the result.  `constraints=true` does the same with the constraint log (`set_mpc_con_log!`) and
+appends `mpc_constraints(bp)` behind it.
 """
-function mpc_solve_log!(bp::BatchedGameProblem, steps::Integer; game_id0::Integer=0, schedule=nothing, disturbance=nothing, costs::Bool=false)
+function mpc_solve_log!(bp::BatchedGameProblem, steps::Integer; game_id0::Integer=0, schedule=nothing, disturbance=nothing, costs::Bool=false, constraints::Bool=false)
     sync_options!(bp)
     B = length(bp.probs); n = bp.probs[1].probsize.n; m = bp.probs[1].probsize.m
     iters = zeros(Int64, B); conv = zeros(Int64, B)
@@ -663,21 +665,29 @@ function mpc_solve_log!(bp::BatchedGameProblem, steps::Integer; game_id0::Intege
     cost = nothing
     log0 = costs && mpc_cost_log(bp)
     costs && set_mpc_cost_log!(bp, true)
+    con = nothing
+    klog0 = constraints && mpc_con_log(bp)
+    constraints && set_mpc_con_log!(bp, true)
     try
         with_schedules(bp, "mpc_solve_log!", up) do
             check(ccall((:alg_mpc_solve_log, LIB), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{AlgGameStats}),
                         bp.h, steps, game_id0, states, controls, stats))
             costs && (cost = mpc_costs(bp))
+            constraints && (con = mpc_constraints(bp))
         end
     finally
         costs && !log0 && set_mpc_cost_log!(bp, false)
+        constraints && !klog0 && set_mpc_con_log!(bp, false)
     end
     check(ccall((:alg_mpc_totals, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Int32), bp.h, iters, conv, 0))
     pull_results!(bp, stats[:, end])                                # the last solve's iterate, multipliers and statistics
     for (g, pr) in enumerate(bp.probs)
         pr.x0 = SVector{n}(states[:, g, end])
     end
-    return costs ? (iters, conv, states, controls, stats, cost) : (iters, conv, states, controls, stats)
+    out = (iters, conv, states, controls, stats)
+    costs && (out = (out..., cost))
+    constraints && (out = (out..., con))
+    return out
 end
 
 # ---- step-wise entry points on a handle (same names as the reference's functions they batch) ------------------------------------
@@ -781,6 +791,56 @@ function mpc_costs(bp::BatchedGameProblem)
     stage = zeros(3, p, B, Int(knots[])); total = zeros(3, p, B)
     check(ccall((:alg_mpc_get_cost, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ref{Int32}), bp.h, knots[], stage, total, knots))
     return stage, total
+end
+
+"""
+    constraint_values(bp; trial=false) -> vals
+
+The constraint values of the plan, read-only, evaluated on the device (alg_get_con_values): con_len x B in the ABI's constraint layout --
+`evaluate!(game_con, traj)` (constraints_methods.jl:329-379) without the dual and penalty update; c <= 0 is feasible, a row of an infinite
+bound reports -Inf, an inert row 0.  `trial=true` evaluates `pdtraj_trial`.  Nothing on the handle changes.  `con_knot_len(bp)` is K1, the
+rows of one step: con_len = (N - 1) K1.
+"""
+function constraint_values(bp::BatchedGameProblem; trial::Bool=false)
+    len = Ref{Int32}(0)
+    check(ccall((:alg_get_con_len, LIB), Cint, (Ptr{Cvoid}, Ref{Int32}), bp.h, len))
+    vals = zeros(Int(len[]), length(bp.probs))
+    check(ccall((:alg_get_con_values, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), bp.h, trial ? 1 : 0, vals))
+    return vals
+end
+function con_knot_len(bp::BatchedGameProblem)
+    len = Ref{Int32}(0)
+    check(ccall((:alg_con_knot_len, LIB), Cint, (Ptr{Cvoid}, Ref{Int32}), bp.h, len))
+    return Int(len[])
+end
+"""
+    set_mpc_con_log!(bp, on)
+
+The closed-loop constraint log of `mpc_solve!` / `mpc_solve_log!` (alg_mpc_set_con_log; off by default): with it on the loop also evaluates,
+on the device, the constraint rows of every plant knot -- with the schedule rows the knot's solve used.  `mpc_constraints(bp)` reads it.
+"""
+set_mpc_con_log!(bp::BatchedGameProblem, on::Bool) = check(ccall((:alg_mpc_set_con_log, LIB), Cint, (Ptr{Cvoid}, Int32), bp.h, on ? 1 : 0))
+function mpc_con_log(bp::BatchedGameProblem)
+    on = Ref{Int32}(0)
+    check(ccall((:alg_mpc_get_con_log, LIB), Cint, (Ptr{Cvoid}, Ref{Int32}), bp.h, on))
+    return on[] != 0
+end
+"""
+    mpc_constraints(bp) -> (vals, worst, first) or nothing
+
+The constraint log of the most recent `mpc_solve!` / `mpc_solve_log!` (alg_mpc_get_con): `vals` is K1 x B x knots -- the rows of one step
+in the knot layout, the control-bound rows on the control applied over the knot, every other row on the state the knot reaches --, `worst`
+7 x B the maximum of every ALG_CON_* kind's rows over the run (-Inf: kind not added), `first` 7 x B the first knot (0-based, as the ABI
+counts) with a row that is not <= 0, -1 if none.  `nothing` while there is no log (see `mpc_costs`).
+"""
+function mpc_constraints(bp::BatchedGameProblem)
+    B = length(bp.probs); K1 = con_knot_len(bp)
+    knots = Ref{Int32}(0)
+    check(ccall((:alg_mpc_get_con, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ref{Int32}), bp.h, 0, C_NULL, C_NULL, C_NULL, knots))
+    knots[] == 0 && return nothing
+    vals = zeros(K1, B, Int(knots[])); worst = zeros(7, B); first = zeros(Int32, 7, B)
+    check(ccall((:alg_mpc_get_con, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ref{Int32}), bp.h, knots[], vals, worst, first, knots))
+    return vals, worst, first
 end
 
 "Give the inspection entry points' device scratch (dense Jacobians, MPC state logs) back to the allocator."

@@ -386,6 +386,32 @@ int alg_get_violation_profile(alg_handle* h, double* dyn, double* con, double* s
  * The call changes nothing on the handle: trajectories, multipliers, statistics, history, profiles, step records and the direction-gate
  * figures stay as they are.  Uses the inspection scratch (alg_release_scratch). */
 int alg_get_cost(alg_handle* h, int32_t which /* ALG_TRAJ_PD | ALG_TRAJ_TRIAL */, double* total /* B x p x 3, or NULL */, double* stage /* B x N x p x 3, or NULL */);
+/* The constraint values of the plan, read-only: evaluate!(game_con, traj) (constraints_methods.jl:329-379) at ALG_TRAJ_PD or ALG_TRAJ_TRIAL,
+ * without the dual and penalty update alg_dual_penalty_update performs with it.  vals: B x alg_get_con_len, the constraint layout at the top
+ * of this file, row semantics of alg_dual_penalty_update's vals: c <= 0 is feasible, a row of an infinite bound reports -inf, an inert row
+ * (a pair never added, a table entry whose player bit is clear) 0.
+ * THE KNOT LAYOUT.  Every block of the constraint vector is per step, so con_len = (N - 1) * K1 with K1 = alg_con_knot_len the rows of
+ * one step; step k pairs the control u_k with the state x_{k+1} it reaches.  One step's rows, in the ABI's order within each block:
+ *   [ collision pair q = 0 .. p(p-1)-1 | u - u_max (m) | u_min - u (m) | per player i: state bound (x - x_max)(n), (x_min - x)(n)
+ *     | per player i: walls | per player i: circles | per player i: 3-D walls | per player i: cylinders ]
+ * with the blocks alg_get_con_len counts: the two base blocks always (a base block that was not added reports 0), the others once added.
+ * The kinds of rows, in layout order: */
+#define ALG_CON_COLLISION 0
+#define ALG_CON_CONTROL   1
+#define ALG_CON_STATE     2
+#define ALG_CON_WALL      3
+#define ALG_CON_CIRCLE    4
+#define ALG_CON_WALL3D    5
+#define ALG_CON_CYLINDER  6
+#define ALG_CON_KINDS     7
+/* The numbers are the handle's or the game's scenario block, in both alg_set_scenario_kernels modes.  One launch, one wavefront per game
+ * whatever kernels the handle solves with; a game's rows do not depend on the batch size or on its place in the batch, bit for bit.
+ * Non-finite input gives non-finite rows for that game only; no status is set.
+ * ALG_ERR_ARG, with nothing changed, for a null handle, a null vals or another `which`; ALG_ERR_STATE if alg_set_x0 was not called.
+ * The call changes nothing on the handle: trajectories, multipliers, penalties, the stored constraint values, statistics, history, profiles,
+ * step records and the direction-gate figures stay as they are.  Uses the inspection scratch (alg_release_scratch). */
+int alg_get_con_values(alg_handle* h, int32_t which /* ALG_TRAJ_PD | ALG_TRAJ_TRIAL */, double* vals /* B x con_len */);
+int alg_con_knot_len(alg_handle* h, int32_t* len /* K1 = con_len / (N - 1) */);
 /* Δtraj = -lu(jac) \ res ; set_traj!(Δpdtraj, Δtraj) (solver_methods.jl:87-88).  delta: B x S or NULL. */
 int alg_newton_direction(alg_handle* h, double reg, double* delta, int32_t* status /*B or NULL*/);
 /* KKT solves with many right-hand sides at the current iterate: J X = R with J the (regularised) residual Jacobian of
@@ -590,6 +616,33 @@ int alg_mpc_plant_advance(alg_handle* h, int32_t knot);
 int alg_mpc_set_cost_log(alg_handle* h, int32_t on);
 int alg_mpc_get_cost_log(alg_handle* h, int32_t* on);
 int alg_mpc_get_cost(alg_handle* h, int32_t max_knots, double* stage /* knots x B x p x 3, or NULL */, double* total /* B x p x 3, or NULL */, int32_t* knots_out);
+/* The closed-loop CONSTRAINT LOG of the fused loop: did the run stay feasible?  As with the cost log, states and controls alone do not
+ * determine it: the constraint numbers of a knot are those of the schedule row its solve used, or of per-game blocks that live on the
+ * device, and after the loop only the last row is left in the blocks.  With the log on (default off) alg_mpc_solve / alg_mpc_solve_log
+ * behave as with the cost log: the state and control logs stay on the device whether or not the caller asks for them, one more kernel is
+ * queued behind the loop (behind the cost kernel if both logs are on) on the same stream, and a call with three NULL output pointers stays
+ * asynchronous.  Plant knot q = t*hold + j of solve t, in the knot layout of alg_get_con_values (K1 = alg_con_knot_len rows):
+ *   the control-bound rows are evaluated on controls[q], the control applied over the knot; every other row on states[q + 1], the state the
+ *   knot reaches, disturbance included -- the (u_k, x_{k+1}) pairing of a step of the constraint layout.  Every number comes from row
+ *   min(t, rows - 1) of the kind's schedule (ALG_SCEN_COLLISION_RADIUS, _CONTROL_BOUND, _STATE_BOUND, _WALL, _CIRCLE, _WALL3D, _CYLINDER) if
+ *   one is set, else from the game's block or the handle's values: the planner's own view in solve t, the convention of the cost log.
+ *   Masks, pair sets, cylinder axes and the +-inf pattern are the handle's.
+ * alg_mpc_get_con waits for the stream.  *knots_out = the plant knots of the most recent loop;
+ *   vals   the first min(max_knots, *knots_out) knots, knots x B x K1;
+ *   worst  B x ALG_CON_KINDS: the maximum of the kind's rows over ALL knots of the run; -inf for a kind that was not added, NaN if any of
+ *          the kind's rows is NaN;
+ *   first  B x ALG_CON_KINDS: the smallest q at which a row of the kind satisfies !(c <= 0) (a NaN counts), -1 if there is none;
+ * any of the three may be NULL; worst and first cover the whole run whatever max_knots is.
+ * States, controls, statistics, totals and everything the loop leaves on the handle are bit-identical with the log on and off; cost log and
+ * constraint log may be on together.  The log lives in a buffer of the handle's own (knots x B x K1 doubles plus the summary), grown on
+ * demand and freed when the log is switched off; a run whose log would exceed 1 GiB is refused with ALG_ERR_ARG before anything is launched.
+ * The log belongs to the most recent loop and to the data it ran with: what invalidates the cost log invalidates it (any adder, alg_set_lqr,
+ * alg_set_scenario_data, alg_mpc_set_schedule) -- *knots_out = 0 and nothing is written -- until the next loop.  With the log off: ALG_OK
+ * and *knots_out = 0.  IBR and the step-wise MPC calls have no log. */
+int alg_mpc_set_con_log(alg_handle* h, int32_t on);
+int alg_mpc_get_con_log(alg_handle* h, int32_t* on);
+int alg_mpc_get_con(alg_handle* h, int32_t max_knots, double* vals /* knots x B x K1, or NULL */, double* worst /* B x 7, or NULL */,
+                    int32_t* first /* B x 7, or NULL */, int32_t* knots_out);
 
 #ifdef __cplusplus
 }
