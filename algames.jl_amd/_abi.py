@@ -27,6 +27,10 @@ ALG_SCHED_DISTURBANCE = 101     # alg_mpc_set_schedule: w (n) per MPC step and g
 ALG_PLANT_RK2, ALG_PLANT_RK4 = 0, 1    # alg_mpc_set_plant: the plant's integrator
 PLANT_INTEGRATORS = ("rk2", "rk4")
 ALG_KKT_RHS_USER, ALG_KKT_RHS_X0, ALG_KKT_RHS_XF = 0, 1, 2    # alg_kkt_solve: the right-hand sides' kind
+# alg_kkt_sensitivity: the parameter vector theta of X = -J^-1 d res / d theta
+(ALG_PARAM_X0, ALG_PARAM_XF, ALG_PARAM_Q, ALG_PARAM_R, ALG_PARAM_UF, ALG_PARAM_COLLISION_COST, ALG_PARAM_COLLISION_RADIUS,
+ ALG_PARAM_CONTROL_BOUND) = range(8)
+PARAM_KINDS = ("x0", "xf", "Q", "R", "uf", "collision_cost", "collision_radius", "control_bound")
 SCEN_KINDS = ("collision_radius", "collision_cost", "control_bound", "state_bound", "wall", "circle", "wall3d", "cylinder")
 # kinds of constraint rows, in the order of the knot layout (alg_get_con_values, alg_mpc_get_con: the columns of worst / first)
 (ALG_CON_COLLISION, ALG_CON_CONTROL, ALG_CON_STATE, ALG_CON_WALL, ALG_CON_CIRCLE, ALG_CON_WALL3D, ALG_CON_CYLINDER) = range(7)
@@ -142,6 +146,8 @@ SIGNATURES = {
     "get_violation_profile": (C.c_int, [_P, _D, _D, _D, _D]),
     "newton_direction": (C.c_int, [_P, C.c_double, _D, _I]),
     "kkt_solve": (C.c_int, [_P, C.c_double, C.c_int32, C.c_int32, _D, C.c_int32, C.c_int32, _D, _I]),
+    "param_len": (C.c_int, [_P, C.c_int32, _I]),
+    "kkt_sensitivity": (C.c_int, [_P, C.c_double, C.c_int32, C.c_int32, _D, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D, _I]),
     "line_search": (C.c_int, [_P, C.c_double, _D, _D, _I]),
     "update_traj": (C.c_int, [_P, C.c_int32, C.c_int32, _D]),
     "record_stats": (C.c_int, [_P, _P]),
@@ -187,6 +193,7 @@ SIGNATURES = {
 # raises AlgamesError naming the backend.
 OPTIONAL = frozenset({"scenario_data_len", "set_scenario_data", "get_scenario_data", "set_scenario_kernels", "get_scenario_kernels",
                       "mpc_set_schedule", "mpc_get_schedule", "mpc_solve_log", "mpc_set_plant", "mpc_get_plant", "mpc_plant_advance", "kkt_solve",
+                      "param_len", "kkt_sensitivity",
                       "set_history_profiles", "get_history_profiles", "get_history_vio",
                       "get_cost", "mpc_set_cost_log", "mpc_get_cost_log", "mpc_get_cost",
                       "get_con_values", "con_knot_len", "mpc_set_con_log", "mpc_get_con_log", "mpc_get_con"})
@@ -651,6 +658,53 @@ class Batch:
             r = None; nrhs = self.n if code == ALG_KKT_RHS_X0 else self.p * self.ni
         X = np.empty((max(cnt, 0), nrhs, self.S)); st = np.empty(max(cnt, 0), dtype=np.int32)
         self.lib.check(self.lib.kkt_solve(self.h, float(reg), code, nrhs, _dptr(r), first, cnt, _dptr(X), _iptr(st)))
+        return X, st
+
+    @staticmethod
+    def _param_code(param):
+        code = PARAM_KINDS.index(param) if isinstance(param, str) and param in PARAM_KINDS else param
+        if isinstance(code, bool) or not isinstance(code, (int, np.integer)) or not 0 <= int(code) < len(PARAM_KINDS):
+            raise ValueError(f"unknown parameter {param!r}: one of {PARAM_KINDS} or its ALG_PARAM_* code")
+        return int(code)
+
+    def param_len(self, param):
+        """entries of the parameter vector `param` (a name of PARAM_KINDS or an ALG_PARAM_* code), in the order of its setter (alg_param_len)"""
+        v = C.c_int32()
+        self.lib.check(self.lib.param_len(self.h, self._param_code(param), C.byref(v)))
+        return v.value
+
+    def _param_len(self, code):
+        """the same count from the problem sizes: what the argument checks use before any library call"""
+        return (self.n, self.p * self.ni, self.p * self.ni, self.p * self.mi, self.p * self.mi, 2 * self.p, self.p * self.p, 2 * self.m)[code]
+
+    def kkt_sensitivity(self, param, reg=0.0, games=None, steps=None, dirs=None):
+        """X = -J^-1 d res / d theta at the current iterate with the right-hand sides built on the device (alg_kkt_sensitivity): theta = `param`
+        (PARAM_KINDS: "x0", "xf", "Q", "R", "uf" in the orders of set_lqr, "collision_cost" / "collision_radius" / "control_bound" in the orders of
+        set_scenario_data), multipliers, penalties and active sets held, J and reg as in kkt_solve.
+        dirs = None: the param_len(param) unit columns.  dirs[cnt, ndir, len] (or [cnt, len]: one direction): column c is the directional
+        derivative X dirs[g, c], one elimination each.  games = (first, count).  steps = (first, count), 0-based: only those steps' blocks
+        of b = n + m + n p rows are stored and downloaded.  Returns (X[cnt, ncol, count * b] in horizontal order, status[cnt])."""
+        code = self._param_code(param)
+        ln = self._param_len(code)
+        first, cnt = (0, self.B) if games is None else (int(games[0]), int(games[1]))
+        if first < 0 or cnt < 1 or first + cnt > self.B:
+            raise ValueError(f"games = (first, count) must lie inside the batch of {self.B}, got {games!r}")
+        s0, ns = (0, self.N - 1) if steps is None else (int(steps[0]), int(steps[1]))
+        if s0 < 0 or ns < 1 or s0 + ns > self.N - 1:
+            raise ValueError(f"steps = (first, count) must lie inside 0 ... {self.N - 2}, got {steps!r}")
+        if dirs is None:
+            v = None; ndir = 0; ncol = ln
+        else:
+            v = np.asarray(dirs, dtype=np.float64)
+            if v.ndim == 2:
+                v = v[:, None, :]
+            if v.ndim != 3 or v.shape[0] != cnt or v.shape[1] < 1 or v.shape[2] != ln:
+                raise ValueError(f"expected shape {(cnt, 'ndir', ln)}, got {tuple(np.shape(dirs))}")
+            if not np.isfinite(v).all():
+                raise ValueError("dirs must be finite")
+            v = _f64(v, v.shape); ndir = ncol = v.shape[1]
+        X = np.empty((cnt, ncol, ns * self.b)); st = np.empty(cnt, dtype=np.int32)
+        self.lib.check(self.lib.kkt_sensitivity(self.h, float(reg), code, ndir, _dptr(v), first, cnt, s0, ns, _dptr(X), _iptr(st)))
         return X, st
 
     def line_search(self, res_norm, reg=0.0):

@@ -1405,6 +1405,58 @@ int alg_kkt_solve(alg_handle* h, double reg, int32_t kind, int32_t nrhs, const d
     return ALG_OK;
 }
 
+// X = -J^-1 d res / d theta with the right-hand sides built on the device (k_kkt_sens): [dirs | out | status] in the inspection scratch, out
+// sized by the step slice
+static int param_len(const Params& p, int32_t param) {
+    switch (param) {
+    case ALG_PARAM_X0: return p.n;
+    case ALG_PARAM_XF: case ALG_PARAM_Q: return p.p * p.ni;
+    case ALG_PARAM_R: case ALG_PARAM_UF: return p.p * p.mi;
+    case ALG_PARAM_COLLISION_COST: return 2 * p.p;
+    case ALG_PARAM_COLLISION_RADIUS: return p.p * p.p;
+    case ALG_PARAM_CONTROL_BOUND: return 2 * p.m;
+    }
+    return -1;
+}
+int alg_param_len(alg_handle* h, int32_t param, int32_t* len) {
+    if (!h || !len) return fail(ALG_ERR_ARG, "alg_param_len: null argument");
+    const int l = param_len(H->pr, param);
+    if (l < 0) return fail(ALG_ERR_ARG, "alg_param_len: unknown parameter " + std::to_string(param));
+    *len = l; return ALG_OK;
+}
+int alg_kkt_sensitivity(alg_handle* h, double reg, int32_t param, int32_t ndir, const double* dirs, int32_t first_game, int32_t n_games, int32_t first_step,
+                        int32_t n_steps, double* out, int32_t* status) {
+    NEED_HANDLE("alg_kkt_sensitivity");
+    const Params& p = H->pr;
+    const int len = param_len(p, param), K = p.N - 1;
+    if (len < 0) return fail(ALG_ERR_ARG, "alg_kkt_sensitivity: unknown parameter " + std::to_string(param));
+    if (!out) return fail(ALG_ERR_ARG, "alg_kkt_sensitivity: null out");
+    if (first_game < 0 || n_games < 1 || (long long)first_game + n_games > p.B) return fail(ALG_ERR_ARG, "alg_kkt_sensitivity: game range outside the batch");
+    if (first_step < 0 || n_steps < 0 || (long long)first_step + n_steps > K || (n_steps == 0 && first_step != 0))
+        return fail(ALG_ERR_ARG, "alg_kkt_sensitivity: step range outside 0 ... N - 2 (n_steps = 0 with first_step = 0: all steps)");
+    if (n_steps == 0) n_steps = K;
+    if (dirs ? ndir < 1 : ndir != 0) return fail(ALG_ERR_ARG, "alg_kkt_sensitivity: ndir must be >= 1 with dirs and 0 without");
+    const int ncol = dirs ? ndir : len;
+    const size_t n_dir = dirs ? (size_t)n_games * ndir * len : 0;
+    for (size_t e = 0; e < n_dir; e++)
+        if (!std::isfinite(dirs[e])) return fail(ALG_ERR_ARG, "alg_kkt_sensitivity: game " + std::to_string(first_game + e / ((size_t)ndir * len)) + ", direction " + std::to_string(e / len % ndir) + ": dirs must be finite");
+    if (param >= ALG_PARAM_XF && param <= ALG_PARAM_UF && !H->lqr_set) return fail(ALG_ERR_STATE, "alg_kkt_sensitivity: LQR data not set");
+    if (param == ALG_PARAM_COLLISION_COST && !p.has_colcost) return fail(ALG_ERR_STATE, "alg_kkt_sensitivity: no collision cost on the handle");
+    if (param == ALG_PARAM_COLLISION_RADIUS && !p.has_colavoid) return fail(ALG_ERR_STATE, "alg_kkt_sensitivity: no collision avoidance on the handle");
+    if (param == ALG_PARAM_CONTROL_BOUND && !p.has_ctl) return fail(ALG_ERR_STATE, "alg_kkt_sensitivity: no control bound on the handle");
+    const size_t per = (size_t)n_steps * (size_t)(p.n + p.m + p.n * p.p);
+    const size_t b_dir = sizeof(double) * n_dir, b_col = sizeof(double) * (size_t)n_games * ncol * per;
+    int rc = use_device(H); if (rc) return rc;
+    if ((rc = ensure_scratch(H, b_dir + b_col + sizeof(int) * (size_t)n_games))) return rc;
+    char* const d = (char*)H->d_scratch;
+    if (dirs && (rc = h2d(H, d, dirs, b_dir))) return rc;
+    LAUNCH_GRID(n_games, k_kkt_sens, H->pr, reg, (int)param, (int)ncol, (int)len, (const double*)(dirs ? d : nullptr), (int)first_game, (int)first_step, (int)n_steps,
+                (double*)(d + b_dir), (int*)(d + b_dir + b_col));
+    if ((rc = d2h(H, out, d + b_dir, b_col))) return rc;
+    if (status && (rc = d2h(H, status, d + b_dir + b_col, sizeof(int) * (size_t)n_games))) return rc;
+    return ALG_OK;
+}
+
 int alg_line_search(alg_handle* h, double reg, const double* rn, double* alpha, int32_t* j) {
     if (!h || !rn || !alpha || !j) return fail(ALG_ERR_ARG, "alg_line_search: null argument");
     int rc = use_device(H); if (rc) return rc;

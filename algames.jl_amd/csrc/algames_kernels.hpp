@@ -594,6 +594,8 @@ __global__ void __launch_bounds__(WAVE, C::WPE) k_kkt_solve(Params pr_arg, doubl
 #include "algames_cost.hpp"
 // Constraint values of a plan and of a closed-loop run, row by row (k_con_values, k_closed_loop_con)
 #include "algames_con.hpp"
+// Equilibrium sensitivities to objective and constraint parameters (k_kkt_sens, the sibling of k_kkt_solve)
+#include "algames_sens.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // Instantiation lists: X(model, p, d, ext)
@@ -780,7 +782,10 @@ __global__ void __launch_bounds__(WAVE, C::WPE) k_kkt_solve(Params pr_arg, doubl
 #define ALG_DEFINE_PLANT(M, P, D, E) ALG_INSTANTIATE_PLANT(template, M, P, D, E)
 #define ALG_DECLARE_PLANT(M, P, D, E) ALG_INSTANTIATE_PLANT(extern template, M, P, D, E)
 #define ALG_DECLARE_SCHED_MW(M, P, D, E, W) ALG_INSTANTIATE_SCHED_MW(extern template, M, P, D, E, W)
-// The KKT solves with many right-hand sides (k_kkt_solve): one per configuration that has a k_direction, in units of their own
-#define ALG_INSTANTIATE_KKT(PREFIX, M, P, D, E) PREFIX __global__ void k_kkt_solve<Cfg<M, P, D, E>>(Params, double, int, int, const double*, int, double*, int*);
+// The KKT solves with many right-hand sides (k_kkt_solve) and their parameter-sensitivity siblings (k_kkt_sens): one of each per configuration
+// that has a k_direction, in units of their own
+#define ALG_INSTANTIATE_KKT(PREFIX, M, P, D, E)                                                                            \
+    PREFIX __global__ void k_kkt_solve<Cfg<M, P, D, E>>(Params, double, int, int, const double*, int, double*, int*);      \
+    PREFIX __global__ void k_kkt_sens<Cfg<M, P, D, E>>(Params, double, int, int, int, const double*, int, int, int, double*, int*);
 #define ALG_DEFINE_KKT(M, P, D, E) ALG_INSTANTIATE_KKT(template, M, P, D, E)
 #define ALG_DECLARE_KKT(M, P, D, E) ALG_INSTANTIATE_KKT(extern template, M, P, D, E)

@@ -983,25 +983,34 @@ def residual_jacobian(prob, reg=0.0, games=None):
 class EquilibriumSensitivity:
     """d z* / d theta of a batch of games: `dz` is (cnt, S, q) in the horizontal order of Δtraj (rows) by the q entries of theta (columns);
     `status` (cnt,) is the per-game status of the solves (0 = every column solved).  The accessors slice rows by the index maps of
-    horizontal_indices: knots and steps are 1-based like the reference's stamps."""
+    horizontal_indices: knots and steps are 1-based like the reference's stamps.  steps = (first, count), 0-based: `dz` holds the rows of
+    those steps only (parameter_sensitivity(steps=...)), count * b of them, and the accessors raise IndexError outside the slice."""
 
-    def __init__(self, dz, status, wrt, N, n, p, mi):
+    def __init__(self, dz, status, wrt, N, n, p, mi, steps=None):
         self.dz, self.status, self.wrt = dz, status, wrt
         self.N, self.n, self.p, self.mi = N, n, p, mi
         self._b = n + p * mi + p * n
+        self.steps = (0, N - 1) if steps is None else (int(steps[0]), int(steps[1]))
+
+    def _row(self, step, what):
+        """first row of the block of 0-based step `step` inside dz"""
+        s0, ns = self.steps
+        if not s0 <= step < s0 + ns:
+            raise IndexError(f"{what}: the sensitivity holds steps {s0 + 1} ... {s0 + ns} only")
+        return (step - s0) * self._b
 
     def dx(self, k):
         """d x_k / d theta, (cnt, n, q), knots k = 2 ... N (x_1 is the initial state itself)."""
         if not 2 <= k <= self.N:
             raise IndexError(f"state knot {k}: 2 ... {self.N}")
-        o = (k - 2) * self._b
+        o = self._row(k - 2, f"state knot {k}")
         return self.dz[:, o:o + self.n, :]
 
     def du(self, k, i=None):
         """d u_k / d theta, steps k = 1 ... N - 1: (cnt, m, q) in the stored order of get_traj (player by player), or player i's (cnt, mi, q)."""
         if not 1 <= k <= self.N - 1:
             raise IndexError(f"control step {k}: 1 ... {self.N - 1}")
-        o = (k - 1) * self._b + self.n
+        o = self._row(k - 1, f"control step {k}") + self.n
         if i is None:
             return self.dz[:, o:o + self.p * self.mi, :]
         if not 1 <= i <= self.p:
@@ -1012,7 +1021,7 @@ class EquilibriumSensitivity:
         """d lambda_{i,k} / d theta (player i's multiplier of the dynamics of step k = 1 ... N - 1), (cnt, n, q)."""
         if not 1 <= k <= self.N - 1 or not 1 <= i <= self.p:
             raise IndexError(f"multiplier (player {i}, step {k}): players 1 ... {self.p}, steps 1 ... {self.N - 1}")
-        o = (k - 1) * self._b + self.n + self.p * self.mi + (i - 1) * self.n
+        o = self._row(k - 1, f"multiplier step {k}") + self.n + self.p * self.mi + (i - 1) * self.n
         return self.dz[:, o:o + self.n, :]
 
     dlam = dλ
@@ -1048,6 +1057,24 @@ def feedback_gains(prob, games=None):
     `controls` log of mpc_rollout), columns the entries of the initial state.  u_1(x0 + e) = u_1 + K e to first order, with multipliers and
     penalties held; exact for the double integrator, Gauss-Newton for the other models (equilibrium_sensitivity)."""
     return np.ascontiguousarray(equilibrium_sensitivity(prob, "x0", 0.0, games).du(1))
+
+
+def parameter_sensitivity(prob, wrt, reg=0.0, games=None, steps=None, directions=None):
+    """How the equilibrium at pdtraj moves with a parameter of the objectives or the constraints: d z* / d theta = -J^-1 d res / d theta with
+    the right-hand sides built on the device (alg_kkt_sensitivity), one launch.  wrt: "x0", "xf", "Q", "R", "uf" (the orders of set_lqr),
+    "collision_cost" (radius (p) | mu (p)), "collision_radius" (p x p ordered pairs), "control_bound" (u_max (m) | u_min (m)) -- the numbers a
+    game was assembled with: per-game LQR data, its scenario block, else the handle's values.  The meaning is equilibrium_sensitivity's:
+    multipliers, penalties and active sets are HELD, J is the reference's Jacobian (exact for the double integrator, Gauss-Newton otherwise).
+    directions = None: one column per entry of theta.  directions[cnt, ndir, len] (or [cnt, len]): the columns are the directional
+    derivatives along those vectors of parameter space, one elimination each.  steps = (first, count), 0-based steps: only their rows are
+    computed into the output and downloaded (steps=(0, 1) with wrt="x0" is the feedback gain and the first state's sensitivity alone).
+    games = (first, count).  Returns an EquilibriumSensitivity over the slice; `.dz` is (cnt, count * b, q)."""
+    if wrt not in _abi.PARAM_KINDS:
+        raise ValueError(f"wrt must be one of {_abi.PARAM_KINDS}, got {wrt!r}")
+    prob._sync_options()
+    b = prob.batch
+    X, st = b.kkt_sensitivity(wrt, reg, games, steps, directions)
+    return EquilibriumSensitivity(np.ascontiguousarray(X.transpose(0, 2, 1)), st, wrt, b.N, b.n, b.p, b.mi, steps)
 
 
 def inner_iteration(prob, LS_count, t_elap, Δ, k, l):

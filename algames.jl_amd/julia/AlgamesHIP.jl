@@ -843,6 +843,48 @@ function mpc_constraints(bp::BatchedGameProblem)
     return vals, worst, first
 end
 
+const PARAM_KINDS = (:x0, :xf, :Q, :R, :uf, :collision_cost, :collision_radius, :control_bound)     # ALG_PARAM_* = index - 1
+function param_code(wrt::Symbol)
+    k = findfirst(==(wrt), PARAM_KINDS)
+    k === nothing && throw(ArgumentError("wrt must be one of $(PARAM_KINDS), got $(wrt)"))
+    return Int32(k - 1)
+end
+"Entries of the parameter vector `wrt` (alg_param_len), in the order of its setter."
+function param_len(bp::BatchedGameProblem, wrt::Symbol)
+    len = Ref{Int32}(0)
+    check(ccall((:alg_param_len, LIB), Cint, (Ptr{Cvoid}, Int32, Ref{Int32}), bp.h, param_code(wrt), len))
+    return Int(len[])
+end
+"""
+    parameter_sensitivity(bp, wrt; reg=0.0, games=nothing, steps=nothing, directions=nothing) -> (X, status)
+
+d z* / d theta = -J^-1 d res / d theta at `pdtraj` with the right-hand sides built on the device (alg_kkt_sensitivity): theta is the initial
+state (`:x0`), the LQR data (`:xf`, `:Q`, `:R`, `:uf`, the orders of the `LQRCost` diagonals), the collision cost (`:collision_cost`, radius
+(p) | mu (p)), the pair radii (`:collision_radius`, p x p ordered pairs) or the control bounds (`:control_bound`, u_max (m) | u_min (m)) --
+the numbers each game was assembled with; multipliers, penalties and active sets are held.  `X` is (count b) x ncol x B in the horizontal
+order of the Newton direction, b = n + m + n p rows per step.  `steps = (first, count)` (0-based steps) stores and downloads those steps'
+rows only.  `directions` (len x ndir x B): the columns are the directional derivatives along those vectors, one elimination each; without
+it there is one column per entry of theta.  `games = (first, count)` (0-based) restricts work, `X`, `directions` and `status` to those games
+(B = count).  `status` (B): 0 where every column was solved.  The raw arrays of the ABI come back: the row of (step k, entry e) of a
+slice starting at step s0 is (k - s0) b + e + 1.
+"""
+function parameter_sensitivity(bp::BatchedGameProblem, wrt::Symbol; reg::Float64=0.0, games=nothing, steps=nothing, directions=nothing)
+    ps = bp.probs[1].probsize
+    b = ps.n + ps.m + ps.n * ps.p
+    g0, B = games === nothing ? (0, length(bp.probs)) : (Int(games[1]), Int(games[2]))
+    (g0 >= 0 && B >= 1 && g0 + B <= length(bp.probs)) || throw(ArgumentError("games = (first, count) must lie inside the batch of $(length(bp.probs))"))
+    len = param_len(bp, wrt)
+    s0, ns = steps === nothing ? (0, ps.N - 1) : (Int(steps[1]), Int(steps[2]))
+    (s0 >= 0 && ns >= 1 && s0 + ns <= ps.N - 1) || throw(ArgumentError("steps = (first, count) must lie inside 0 ... $(ps.N - 2)"))
+    ndir = directions === nothing ? 0 : size(directions, 2)
+    directions === nothing || size(directions) == (len, ndir, B) || throw(ArgumentError("directions must be $(len) x ndir x $(B)"))
+    dirs = directions === nothing ? C_NULL : Array{Float64}(directions)
+    X = zeros(ns * b, directions === nothing ? len : ndir, B); status = zeros(Int32, B)
+    check(ccall((:alg_kkt_sensitivity, LIB), Cint, (Ptr{Cvoid}, Float64, Int32, Int32, Ptr{Float64}, Int32, Int32, Int32, Int32, Ptr{Float64}, Ptr{Int32}),
+                bp.h, reg, param_code(wrt), ndir, dirs, g0, B, s0, ns, X, status))
+    return X, status
+end
+
 "Give the inspection entry points' device scratch (dense Jacobians, MPC state logs) back to the allocator."
 release_scratch!(bp::BatchedGameProblem) = check(ccall((:alg_release_scratch, LIB), Cint, (Ptr{Cvoid},), bp.h))
 

@@ -439,6 +439,39 @@ int alg_newton_direction(alg_handle* h, double reg, double* delta, int32_t* stat
 #define ALG_KKT_RHS_XF   2
 int alg_kkt_solve(alg_handle* h, double reg, int32_t kind, int32_t nrhs, const double* rhs /* n_games x nrhs x S, vertical order; NULL unless USER */,
                   int32_t first_game, int32_t n_games, double* out /* n_games x nrhs x S, horizontal order */, int32_t* status /* n_games or NULL */);
+/* Equilibrium sensitivities to objective and constraint parameters: X = -J^-1 d res / d theta at pdtraj, with J, reg, the refinement gate and
+ * the per-game status rule of alg_kkt_solve, and the right-hand sides R = -d res / d theta built on the device: evaluated at pdtraj with the
+ * game's multipliers and penalties (and the active sets behind them) held, from the numbers the game was assembled with -- per-game LQR data
+ * (alg_set_lqr(per_game = 1)), the game's scenario block in both alg_set_scenario_kernels modes, else the handle's values.
+ *   theta = one of the parameter vectors below, `len` = alg_param_len entries in the order of the setter named there.
+ *   dirs == NULL (ndir must be 0): the len unit columns, ncol = len.
+ *   dirs != NULL (ndir >= 1):      column c of game g is the directional derivative X v for v = dirs[g][c] (len finite doubles): one
+ *                                  elimination per direction whatever len is; ncol = ndir.
+ *   Only the rows of steps first_step .. first_step + n_steps - 1 (0-based, n_steps = 0 with first_step = 0: all N - 1) are stored and copied
+ *   back: a step's block is b = n + m + n p doubles of the horizontal order (x_{k+1}, u_{.,k}, lambda_{.,k}), out is n_games x ncol x (n_steps b).
+ *   The device scratch and the download are sized by the slice.
+ * Columns of a parameter that does not enter the residual are exactly zero with status OK: a diagonal entry of the pair table, a pair that
+ * was never added, a bound that is +-inf, a row outside its active set (a = (c >= 0) | (lambda > 0) is 0).  The collision cost enters through
+ * the pairs with r_i - |d| > 0 only.
+ * ALG_ERR_ARG, with nothing changed, for a null handle, an unknown param, ndir and dirs that disagree, non-finite dirs, a game range or step
+ * range outside the problem, or a null out; ALG_ERR_STATE, with nothing changed, if the parameter's ingredient is not on the handle (no
+ * alg_set_lqr for XF / Q / R / UF; no collision cost, collision avoidance or control bound for the last three).
+ * What the call leaves behind is what alg_kkt_solve leaves behind: pdtraj, x0, multipliers, penalties, statistics, history and profiles are
+ * untouched; ALG_TRAJ_DELTA holds the last column (all steps of it); ALG_TRAJ_TRIAL is scratch (x_1 restored).  Uses the inspection scratch. */
+#define ALG_PARAM_X0               0   /* n            : x_1                                            */
+#define ALG_PARAM_XF               1   /* p*ni         : xf order of alg_set_lqr                        */
+#define ALG_PARAM_Q                2   /* p*ni         : Qdiag order of alg_set_lqr                     */
+#define ALG_PARAM_R                3   /* p*mi         : Rdiag order                                    */
+#define ALG_PARAM_UF               4   /* p*mi         : uf order                                       */
+#define ALG_PARAM_COLLISION_COST   5   /* 2p           : radius (p) | mu (p), ALG_SCEN_COLLISION_COST   */
+#define ALG_PARAM_COLLISION_RADIUS 6   /* p*p          : ordered pairs, ALG_SCEN_COLLISION_RADIUS       */
+#define ALG_PARAM_CONTROL_BOUND    7   /* 2m           : u_max (m) | u_min (m), ALG_SCEN_CONTROL_BOUND  */
+int alg_param_len(alg_handle* h, int32_t param, int32_t* len);
+int alg_kkt_sensitivity(alg_handle* h, double reg, int32_t param,
+                        int32_t ndir, const double* dirs /* n_games x ndir x len, or NULL */,
+                        int32_t first_game, int32_t n_games,
+                        int32_t first_step, int32_t n_steps /* 0 = all N-1 */,
+                        double* out /* n_games x ncol x (n_steps*b) */, int32_t* status /* n_games or NULL */);
 /* line_search (solver_methods.jl:105-125) on the stored Δpdtraj. */
 int alg_line_search(alg_handle* h, double reg, const double* res_norm /*B*/, double* alpha /*B*/,
                     int32_t* j /*B*/);
