@@ -31,6 +31,7 @@ ALG_KKT_RHS_USER, ALG_KKT_RHS_X0, ALG_KKT_RHS_XF = 0, 1, 2    # alg_kkt_solve: t
 (ALG_PARAM_X0, ALG_PARAM_XF, ALG_PARAM_Q, ALG_PARAM_R, ALG_PARAM_UF, ALG_PARAM_COLLISION_COST, ALG_PARAM_COLLISION_RADIUS,
  ALG_PARAM_CONTROL_BOUND) = range(8)
 PARAM_KINDS = ("x0", "xf", "Q", "R", "uf", "collision_cost", "collision_radius", "control_bound")
+ALG_NORMAL_MAX_COLS = 63    # alg_kkt_normal_equations: columns of one call
 SCEN_KINDS = ("collision_radius", "collision_cost", "control_bound", "state_bound", "wall", "circle", "wall3d", "cylinder")
 # kinds of constraint rows, in the order of the knot layout (alg_get_con_values, alg_mpc_get_con: the columns of worst / first)
 (ALG_CON_COLLISION, ALG_CON_CONTROL, ALG_CON_STATE, ALG_CON_WALL, ALG_CON_CIRCLE, ALG_CON_WALL3D, ALG_CON_CYLINDER) = range(7)
@@ -148,6 +149,7 @@ SIGNATURES = {
     "kkt_solve": (C.c_int, [_P, C.c_double, C.c_int32, C.c_int32, _D, C.c_int32, C.c_int32, _D, _I]),
     "param_len": (C.c_int, [_P, C.c_int32, _I]),
     "kkt_sensitivity": (C.c_int, [_P, C.c_double, C.c_int32, C.c_int32, _D, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _D, _I]),
+    "kkt_normal_equations": (C.c_int, [_P, C.c_double, C.c_int32, _I, _I, _D, _D, C.c_int32, C.c_int32, C.c_int32, _D, _D, _D, _I]),
     "line_search": (C.c_int, [_P, C.c_double, _D, _D, _I]),
     "update_traj": (C.c_int, [_P, C.c_int32, C.c_int32, _D]),
     "record_stats": (C.c_int, [_P, _P]),
@@ -193,7 +195,7 @@ SIGNATURES = {
 # raises AlgamesError naming the backend.
 OPTIONAL = frozenset({"scenario_data_len", "set_scenario_data", "get_scenario_data", "set_scenario_kernels", "get_scenario_kernels",
                       "mpc_set_schedule", "mpc_get_schedule", "mpc_solve_log", "mpc_set_plant", "mpc_get_plant", "mpc_plant_advance", "kkt_solve",
-                      "param_len", "kkt_sensitivity",
+                      "param_len", "kkt_sensitivity", "kkt_normal_equations",
                       "set_history_profiles", "get_history_profiles", "get_history_vio",
                       "get_cost", "mpc_set_cost_log", "mpc_get_cost_log", "mpc_get_cost",
                       "get_con_values", "con_knot_len", "mpc_set_con_log", "mpc_get_con_log", "mpc_get_con"})
@@ -706,6 +708,52 @@ class Batch:
         X = np.empty((cnt, ncol, ns * self.b)); st = np.empty(cnt, dtype=np.int32)
         self.lib.check(self.lib.kkt_sensitivity(self.h, float(reg), code, ndir, _dptr(v), first, cnt, s0, ns, _dptr(X), _iptr(st)))
         return X, st
+
+    def kkt_normal_equations(self, cols, target, weight, reg=0.0, games=None):
+        """The normal equations of fitting parameters to an observed trajectory, reduced on the device (alg_kkt_normal_equations).  cols: up to
+        ALG_NORMAL_MAX_COLS distinct (param, index) pairs, param a name of PARAM_KINDS or its code, index an entry of that parameter vector;
+        column c is the unit column kkt_sensitivity returns for it.  target[cnt, S]: the observed z in horizontal order; weight[S] (shared) or
+        weight[cnt, S]: finite and >= 0.  With r = z - target over the S entries of pdtraj behind x_1, per game: loss = 1/2 sum w r^2,
+        g = X' W r, H = X' W X (both triangles, symmetric bit for bit).  games = (first, count).  Returns (H[cnt, q, q], g[cnt, q], loss[cnt],
+        status[cnt]); no column is downloaded."""
+        first, cnt = (0, self.B) if games is None else (int(games[0]), int(games[1]))
+        if first < 0 or cnt < 1 or first + cnt > self.B:
+            raise ValueError(f"games = (first, count) must lie inside the batch of {self.B}, got {games!r}")
+        cols = list(cols)
+        if not 1 <= len(cols) <= ALG_NORMAL_MAX_COLS:
+            raise ValueError(f"cols must name 1 ... {ALG_NORMAL_MAX_COLS} columns, got {len(cols)}")
+        cp = np.empty(len(cols), dtype=np.int32); ci = np.empty(len(cols), dtype=np.int32)
+        seen = set()
+        for c, col in enumerate(cols):
+            try:
+                if isinstance(col, str):
+                    raise TypeError
+                param, index = col
+            except (TypeError, ValueError):
+                raise ValueError(f"column {c}: expected a (param, index) pair, got {col!r}") from None
+            code = self._param_code(param)
+            if isinstance(index, bool) or not isinstance(index, (int, np.integer)) or not 0 <= int(index) < self._param_len(code):
+                raise ValueError(f"column {c}: index must be an integer in 0 ... {self._param_len(code) - 1} for {PARAM_KINDS[code]!r}, got {index!r}")
+            if (code, int(index)) in seen:
+                raise ValueError(f"column {c}: duplicate column ({PARAM_KINDS[code]!r}, {int(index)})")
+            seen.add((code, int(index)))
+            cp[c], ci[c] = code, int(index)
+        t = np.asarray(target, dtype=np.float64)
+        if t.shape != (cnt, self.S):
+            raise ValueError(f"target: expected shape {(cnt, self.S)}, got {t.shape}")
+        if not np.isfinite(t).all():
+            raise ValueError("target must be finite")
+        w = np.asarray(weight, dtype=np.float64)
+        if w.shape not in ((self.S,), (cnt, self.S)):
+            raise ValueError(f"weight: expected shape {(self.S,)} or {(cnt, self.S)}, got {w.shape}")
+        if not np.isfinite(w).all() or (w < 0).any():
+            raise ValueError("weight must be finite and >= 0")
+        t, w = _f64(t), _f64(w)
+        q = len(cols)
+        Hm = np.empty((cnt, q, q)); g = np.empty((cnt, q)); loss = np.empty(cnt); st = np.empty(cnt, dtype=np.int32)
+        self.lib.check(self.lib.kkt_normal_equations(self.h, float(reg), q, _iptr(cp), _iptr(ci), _dptr(t), _dptr(w), int(w.ndim == 2), first, cnt,
+                                                     _dptr(Hm), _dptr(g), _dptr(loss), _iptr(st)))
+        return Hm, g, loss, st
 
     def line_search(self, res_norm, reg=0.0):
         rn = _f64(res_norm, (self.B,)); a = np.empty(self.B); j = np.empty(self.B, dtype=np.int32)

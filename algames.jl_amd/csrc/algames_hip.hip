@@ -74,6 +74,9 @@ __global__ void __launch_bounds__(WAVE) k_vio_profile(Params pr_arg, double* out
     }
 }
 
+// the weighted Gram matrix of sensitivity columns and the fit residual (k_sens_gram): model-independent as well
+#include "algames_normal.hpp"
+
 // ------------------------------------------------------------------------------------------------
 // Host side
 // ------------------------------------------------------------------------------------------------
@@ -1454,6 +1457,87 @@ int alg_kkt_sensitivity(alg_handle* h, double reg, int32_t param, int32_t ndir, 
                 (double*)(d + b_dir), (int*)(d + b_dir + b_col));
     if ((rc = d2h(H, out, d + b_dir, b_col))) return rc;
     if (status && (rc = d2h(H, status, d + b_dir + b_col, sizeof(int) * (size_t)n_games))) return rc;
+    return ALG_OK;
+}
+
+// The normal equations of a fit (k_sens_gram over the columns of k_kkt_sens): the columns are grouped by parameter kind in the order the kinds
+// first appear; a kind's columns are one k_kkt_sens launch with dirs = the selected unit vectors into the kind's own segment, and one
+// k_sens_gram launch reduces all segments.  Scratch: [column table | dirs | columns | target | weight | H | g | loss | status per launch |
+// status]; one upload of table and dirs, one each of target and weight; H, g, loss and status come back.  The checks that read the handle
+// come before the scans of target and weight.
+int alg_kkt_normal_equations(alg_handle* h, double reg, int32_t ncol, const int32_t* col_param, const int32_t* col_index, const double* target, const double* weight,
+                             int32_t per_game_weight, int32_t first_game, int32_t n_games, double* Hout, double* gout, double* loss, int32_t* status) {
+    NEED_HANDLE("alg_kkt_normal_equations");
+    const Params& p = H->pr;
+    constexpr int NKIND = ALG_PARAM_CONTROL_BOUND + 1;
+    if (ncol < 1 || ncol > ALG_NORMAL_MAX_COLS) return fail(ALG_ERR_ARG, "alg_kkt_normal_equations: ncol must be 1 ... " + std::to_string(ALG_NORMAL_MAX_COLS));
+    if (!col_param || !col_index) return fail(ALG_ERR_ARG, "alg_kkt_normal_equations: null col_param or col_index");
+    if (!target || !weight || !Hout || !gout || !loss) return fail(ALG_ERR_ARG, "alg_kkt_normal_equations: null target, weight, H, g or loss");
+    if (first_game < 0 || n_games < 1 || (long long)first_game + n_games > p.B) return fail(ALG_ERR_ARG, "alg_kkt_normal_equations: game range outside the batch");
+    struct Group { int param, len; std::vector<int> idx; };
+    std::vector<Group> groups;
+    int gof[NKIND], group_of[ALG_NORMAL_MAX_COLS], pos_of[ALG_NORMAL_MAX_COLS];
+    std::fill(gof, gof + NKIND, -1);
+    for (int c = 0; c < ncol; c++) {
+        const int len = param_len(p, col_param[c]);
+        if (len < 0) return fail(ALG_ERR_ARG, "alg_kkt_normal_equations: column " + std::to_string(c) + ": unknown parameter " + std::to_string(col_param[c]));
+        if (col_index[c] < 0 || col_index[c] >= len) return fail(ALG_ERR_ARG, "alg_kkt_normal_equations: column " + std::to_string(c) + ": index outside 0 ... " + std::to_string(len - 1));
+        for (int e = 0; e < c; e++)
+            if (col_param[e] == col_param[c] && col_index[e] == col_index[c]) return fail(ALG_ERR_ARG, "alg_kkt_normal_equations: columns " + std::to_string(e) + " and " + std::to_string(c) + " name the same entry");
+        if (gof[col_param[c]] < 0) { gof[col_param[c]] = (int)groups.size(); groups.push_back({col_param[c], len, {}}); }
+        group_of[c] = gof[col_param[c]]; pos_of[c] = (int)groups[group_of[c]].idx.size();
+        groups[group_of[c]].idx.push_back(col_index[c]);
+    }
+    for (const Group& gr : groups) {
+        if (gr.param >= ALG_PARAM_XF && gr.param <= ALG_PARAM_UF && !H->lqr_set) return fail(ALG_ERR_STATE, "alg_kkt_normal_equations: LQR data not set");
+        if (gr.param == ALG_PARAM_COLLISION_COST && !p.has_colcost) return fail(ALG_ERR_STATE, "alg_kkt_normal_equations: no collision cost on the handle");
+        if (gr.param == ALG_PARAM_COLLISION_RADIUS && !p.has_colavoid) return fail(ALG_ERR_STATE, "alg_kkt_normal_equations: no collision avoidance on the handle");
+        if (gr.param == ALG_PARAM_CONTROL_BOUND && !p.has_ctl) return fail(ALG_ERR_STATE, "alg_kkt_normal_equations: no control bound on the handle");
+    }
+    const size_t S = (size_t)p.S, n_tgt = (size_t)n_games * S, n_wt = per_game_weight ? n_tgt : S;
+    for (size_t e = 0; e < n_tgt; e++)
+        if (!std::isfinite(target[e])) return fail(ALG_ERR_ARG, "alg_kkt_normal_equations: game " + std::to_string(first_game + e / S) + ": target must be finite");
+    for (size_t e = 0; e < n_wt; e++)
+        if (!std::isfinite(weight[e]) || weight[e] < 0.0) return fail(ALG_ERR_ARG, "alg_kkt_normal_equations: weight " + std::to_string(e) + " must be finite and >= 0");
+    const int ng = (int)groups.size(), q = ncol;
+    constexpr size_t b_tab = sizeof(long long) * 2 * 64;
+    std::vector<size_t> o_dir(ng), o_seg(ng);
+    size_t at = b_tab;
+    for (int k = 0; k < ng; k++) { o_dir[k] = at; at += sizeof(double) * (size_t)n_games * groups[k].idx.size() * groups[k].len; }
+    const size_t b_up = at, o_col = at;
+    for (int k = 0; k < ng; k++) { o_seg[k] = at; at += sizeof(double) * (size_t)n_games * groups[k].idx.size() * S; }
+    const size_t o_tgt = at, o_wt = o_tgt + sizeof(double) * n_tgt, o_H = o_wt + sizeof(double) * n_wt, b_H = sizeof(double) * (size_t)n_games * q * q;
+    const size_t o_g = o_H + b_H, b_g = sizeof(double) * (size_t)n_games * q, o_loss = o_g + b_g, b_loss = sizeof(double) * (size_t)n_games;
+    const size_t b_st = sizeof(int) * (size_t)n_games, o_gst = o_loss + b_loss, o_st = o_gst + b_st * ng, total = o_st + b_st;
+    // column c is column pos_of[c] of its kind's segment; its direction is e_index, for every game
+    std::vector<char> up(b_up, 0);
+    long long* const tab = (long long*)up.data();
+    for (int c = 0; c < q; c++) {
+        const int k = group_of[c], cols_k = (int)groups[k].idx.size();
+        tab[2 * c] = (long long)((o_seg[k] - o_col) / sizeof(double) + (size_t)pos_of[c] * S);
+        tab[2 * c + 1] = (long long)((size_t)cols_k * S);
+        double* const dv = (double*)(up.data() + o_dir[k]);
+        for (int g = 0; g < n_games; g++) dv[((size_t)g * cols_k + pos_of[c]) * groups[k].len + col_index[c]] = 1.0;
+    }
+    int rc = use_device(H); if (rc) return rc;
+    if ((rc = ensure_scratch(H, total))) return rc;
+    char* const d = (char*)H->d_scratch;
+    if ((rc = h2d(H, d, up.data(), b_up))) return rc;
+    if ((rc = h2d(H, d + o_tgt, target, sizeof(double) * n_tgt))) return rc;
+    if ((rc = h2d(H, d + o_wt, weight, sizeof(double) * n_wt))) return rc;
+    for (int k = 0; k < ng; k++) {
+        const Group& gr = groups[k];
+        LAUNCH_GRID(n_games, k_kkt_sens, H->pr, reg, gr.param, (int)gr.idx.size(), gr.len, (const double*)(d + o_dir[k]), (int)first_game, 0, p.N - 1,
+                    (double*)(d + o_seg[k]), (int*)(d + o_gst + b_st * k));
+    }
+    hipLaunchKernelGGL(k_sens_gram, dim3(n_games), dim3(GRAM_WAVES * WAVE), 0, H->stream, H->pr, (const long long*)d, (const double*)(d + o_col), (const double*)(d + o_tgt),
+                       (const double*)(d + o_wt), (int)(per_game_weight != 0), q, (int)first_game, ng, (const int*)(d + o_gst), (double*)(d + o_H), (double*)(d + o_g),
+                       (double*)(d + o_loss), (int*)(d + o_st));
+    if ((rc = launch_check("k_sens_gram"))) return rc;
+    if ((rc = d2h(H, Hout, d + o_H, b_H))) return rc;
+    if ((rc = d2h(H, gout, d + o_g, b_g))) return rc;
+    if ((rc = d2h(H, loss, d + o_loss, b_loss))) return rc;
+    if (status && (rc = d2h(H, status, d + o_st, b_st))) return rc;
     return ALG_OK;
 }
 

@@ -9,6 +9,7 @@ Reference: src/Algames.jl:19-165 (exports), src/problem/problem.jl, src/problem/
 src/struct/*.jl, src/dynamics/{double_integrator,unicycle}.jl, src/objective/objective.jl,
 src/constraints/{game_constraints,constraints_methods}.jl.
 """
+import collections
 import contextlib
 import dataclasses
 import os
@@ -1075,6 +1076,177 @@ def parameter_sensitivity(prob, wrt, reg=0.0, games=None, steps=None, directions
     b = prob.batch
     X, st = b.kkt_sensitivity(wrt, reg, games, steps, directions)
     return EquilibriumSensitivity(np.ascontiguousarray(X.transpose(0, 2, 1)), st, wrt, b.N, b.n, b.p, b.mi, steps)
+
+
+NormalEquations = collections.namedtuple("NormalEquations", "H g loss status cols")
+FitResult = collections.namedtuple("FitResult", "theta loss_history accepted status")
+FIT_KINDS = ("xf", "Q", "R", "uf")            # what fit_parameters writes back through per-game set_lqr
+FIT_DIAG_FLOOR = 1e-12                        # fit_parameters: the damping diagonal is max(diag H, FIT_DIAG_FLOOR max diag H)
+
+
+def normal_columns(batch, wrt):
+    """The (kind, index) columns `wrt` names: a sequence of kinds of PARAM_KINDS ("xf": every entry of it, in order) or (kind, indices) pairs;
+    a single kind may be given as a string."""
+    if isinstance(wrt, str):
+        wrt = (wrt,)
+    cols = []
+    for item in wrt:
+        kind, idx = (item, None) if isinstance(item, str) else (item[0], item[1])
+        if kind not in _abi.PARAM_KINDS:
+            raise ValueError(f"wrt must name kinds of {_abi.PARAM_KINDS}, got {kind!r}")
+        ln = batch._param_len(_abi.PARAM_KINDS.index(kind))
+        cols += [(kind, int(i)) for i in (range(ln) if idx is None else np.atleast_1d(idx))]
+    return cols
+
+
+def _observed_rows(b, observed, cnt):
+    """the observation as (cnt, S) in horizontal order: an array of that shape, or states (cnt, N, n) and controls (cnt, N - 1, m) -- a
+    PrimalDualTraj or a pair; the multiplier rows are zero (the default weight ignores them)"""
+    if hasattr(observed, "states"):
+        observed = (observed.states, observed.controls)
+    if isinstance(observed, (tuple, list)) and len(observed) == 2 and np.ndim(observed[0]) == 3:
+        X, U = (np.asarray(v, dtype=np.float64) for v in observed)
+        if X.shape != (cnt, b.N, b.n) or U.shape != (cnt, b.N - 1, b.m):
+            raise ValueError(f"observed: expected states {(cnt, b.N, b.n)} and controls {(cnt, b.N - 1, b.m)}, got {X.shape} and {U.shape}")
+        return np.ascontiguousarray(b.join_traj(X, U, np.zeros((cnt, b.p, b.N - 1, b.n)))[:, b.n:])
+    t = np.asarray(observed, dtype=np.float64)
+    if t.shape != (cnt, b.S):
+        raise ValueError(f"observed: expected shape {(cnt, b.S)} or a states / controls pair, got {t.shape}")
+    return t
+
+
+def default_fit_weight(b):
+    """1 on the rows of states and controls, 0 on the rows of the dynamics multipliers: (S,) in horizontal order"""
+    return np.ascontiguousarray(b.join_traj(np.ones((1, b.N, b.n)), np.ones((1, b.N - 1, b.m)), np.zeros((1, b.p, b.N - 1, b.n)))[0, b.n:])
+
+
+def normal_scratch_bytes(batch, cols, games, per_game_weight=False):
+    """Bytes of device scratch one alg_kkt_normal_equations call over `games` games takes: the column table, per kind the unit directions
+    and the columns, target, weight, H, g, loss and the status words."""
+    q, S = len(cols), batch.S
+    kinds = collections.Counter(k for k, _ in cols)
+    dirs = sum(c * batch._param_len(_abi.PARAM_KINDS.index(k)) for k, c in kinds.items())
+    per_game = 8 * (dirs + q * S + S + (S if per_game_weight else 0) + q * q + q + 1) + 4 * (len(kinds) + 1)
+    return 1024 + (0 if per_game_weight else 8 * S) + games * per_game
+
+
+def normal_equations(prob, observed, wrt, weight=None, reg=0.0, games=None, max_scratch_bytes=1 << 30):
+    """The normal equations of fitting the parameters `wrt` to an observed trajectory, reduced on the device (alg_kkt_normal_equations): with
+    X the columns d z* / d theta of parameter_sensitivity (multipliers, penalties and active sets held; exact for the double integrator,
+    Gauss-Newton otherwise) and r = z - observed over the S rows of pdtraj behind x_1, per game
+        loss = 1/2 sum w r^2,    g = X' W r,    H = X' W X.
+    wrt: kinds ("xf") or (kind, indices) pairs, up to 63 columns in all, in any mix and order (normal_columns).  observed: (cnt, S) in
+    horizontal order, or a PrimalDualTraj-shaped states / controls pair.  weight: (S,) or (cnt, S), finite and >= 0; None is 1 on states and
+    controls and 0 on the dynamics multipliers.  games = (first, count).  The game range is cut into chunks whose device scratch
+    (normal_scratch_bytes: columns, directions, target, weight and results) stays under max_scratch_bytes -- one game at a time if even that
+    is more; a game's numbers do not depend on the cut, bit for bit.  Call it on a solved problem.
+    Returns NormalEquations(H (cnt, q, q), g (cnt, q), loss (cnt,), status (cnt,), cols); no column is downloaded."""
+    prob._sync_options()
+    b = prob.batch
+    first, cnt = (0, b.B) if games is None else (int(games[0]), int(games[1]))
+    if first < 0 or cnt < 1 or first + cnt > b.B:
+        raise ValueError(f"games = (first, count) must lie inside the batch of {b.B}, got {games!r}")
+    cols = normal_columns(b, wrt)
+    t = _observed_rows(b, observed, cnt)
+    w = default_fit_weight(b) if weight is None else np.asarray(weight, dtype=np.float64)
+    fixed = normal_scratch_bytes(b, cols, 0, w.ndim == 2)
+    step = max(1, (int(max_scratch_bytes) - fixed) // (normal_scratch_bytes(b, cols, 1, w.ndim == 2) - fixed))
+    if step >= cnt:
+        return NormalEquations(*b.kkt_normal_equations(cols, t, w, reg, (first, cnt)), cols)
+    if w.shape not in ((b.S,), (cnt, b.S)):
+        raise ValueError(f"weight: expected shape {(b.S,)} or {(cnt, b.S)}, got {w.shape}")
+    parts = [b.kkt_normal_equations(cols, t[a:a + step], w if w.ndim == 1 else w[a:a + step], reg, (first + a, min(step, cnt - a))) for a in range(0, cnt, step)]
+    return NormalEquations(*(np.concatenate([part[k] for part in parts]) for k in range(4)), cols)
+
+
+def fit_parameters(prob, observed, wrt, weight=None, iters=20, damping=1e-3, reg=0.0):
+    """Fit LQR parameters of every game of the batch to an observed play: a batched Levenberg-Marquardt loop on the device's normal equations,
+    one damping lambda_g per game.  wrt: kinds of FIT_KINDS ("xf", "Q", "R", "uf") or (kind, indices) pairs; theta_0 is prob.game_obj's data.
+    The loop writes theta_0 per game (set_lqr), solves (newton_solve) and forms the normal equations; then, `iters` times:
+        solve (H + lambda_g diag(H)) delta = -g per game (the diagonal floored at FIT_DIAG_FLOOR of its maximum), set theta + delta on every
+        game, run one warm-started newton_solve of the batch and one normal_equations call;
+        game g accepts, with lambda_g /= 10, if its solve converged with status 0, the normal equations' status is 0, the loss fell and every
+        fitted Q and R entry stays > 0; else its theta, pdtraj and constraint duals are put back from host copies and lambda_g *= 10.
+    One solve and one reduction call per iteration; no sensitivity column leaves the device.
+    Scale freedom: multiplying ALL of one player's Q and R by one factor moves no trajectory, so Q and R of a player cannot be fitted
+    together -- fit Q with R held, or R with Q held.
+    Returns FitResult(theta (B, q) in the order of normal_columns(wrt), loss_history (iters + 1, B) -- the loss of the accepted state after
+    every iteration, non-increasing --, accepted (iters, B) bool, status (B,) of the accepted state's normal equations).  The handle is left
+    with the fitted values as per-game LQR data and each game's accepted plan in pdtraj; prob.game_obj is not modified."""
+    b = prob.batch
+    cols = normal_columns(b, wrt)
+    if any(k not in FIT_KINDS for k, _ in cols):
+        raise ValueError(f"fit_parameters: wrt must name kinds of {FIT_KINDS}")
+    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 0 or not (np.isfinite(damping) and damping > 0):
+        raise ValueError("fit_parameters: iters must be an integer >= 0 and damping a positive number")
+    B, q, o = b.B, len(cols), prob.game_obj
+    t = _observed_rows(b, observed, B)
+    data = {"Q": np.array(np.broadcast_to(o.Qdiag, (B, b.p, b.ni)), dtype=np.float64), "xf": np.array(np.broadcast_to(o.xf, (B, b.p, b.ni)), dtype=np.float64),
+            "R": np.array(np.broadcast_to(o.Rdiag, (B, b.p, b.mi)), dtype=np.float64), "uf": np.array(np.broadcast_to(o.uf, (B, b.p, b.mi)), dtype=np.float64)}
+    positive = np.array([k in ("Q", "R") for k, _ in cols])
+
+    def gather():
+        return np.stack([data[k].reshape(B, -1)[:, i] for k, i in cols], axis=1)
+
+    def scatter(theta):
+        for c, (k, i) in enumerate(cols):
+            data[k].reshape(B, -1)[:, i] = theta[:, c]
+        b.set_lqr(data["Q"], data["R"], data["xf"], data["uf"])
+
+    def solve_and_reduce(init):
+        newton_solve(prob, init=init)
+        s = prob.stats.summary
+        ne = normal_equations(prob, t, cols, weight, reg)
+        ok = (s["converged"] == 1) & (s["status"] == 0) & (ne.status == 0) & np.isfinite(ne.loss)
+        return ne, ok
+
+    theta = gather()
+    scatter(theta)
+    ne, _ = solve_and_reduce(True)
+    Hm, g, loss, status = ne.H.copy(), ne.g.copy(), ne.loss.copy(), ne.status.copy()
+    lam = np.full(B, float(damping))
+    history, accepted = [loss.copy()], np.zeros((iters, B), dtype=bool)
+    for it in range(iters):
+        z = b.get_traj()
+        duals = b.get_con_duals() if b.con_len else None
+        delta = lm_step(Hm, g, lam)
+        trial = theta + delta
+        sane = np.all(np.isfinite(trial), axis=1) & np.all(trial[:, positive] > 0, axis=1)
+        trial[~sane] = theta[~sane]
+        scatter(trial)
+        ne, ok = solve_and_reduce(False)
+        acc = sane & ok & (ne.loss < loss)
+        accepted[it] = acc
+        theta[acc] = trial[acc]; Hm[acc] = ne.H[acc]; g[acc] = ne.g[acc]; loss[acc] = ne.loss[acc]; status[acc] = ne.status[acc]
+        lam = np.where(acc, lam / 10.0, lam * 10.0)
+        if not acc.all():                                     # the rejected games go back to their accepted state
+            scatter(theta)
+            z2 = b.get_traj(); z2[~acc] = z[~acc]
+            b.set_traj(z2)
+            if duals is not None:
+                l2, m2 = b.get_con_duals(); l2[~acc] = duals[0][~acc]; m2[~acc] = duals[1][~acc]
+                b.set_con_duals(l2, m2)
+        history.append(loss.copy())
+    return FitResult(theta, np.stack(history), accepted, status)
+
+
+def lm_step(Hm, g, lam):
+    """delta of (H + lambda diag(H)) delta = -g per game, the diagonal floored at FIT_DIAG_FLOOR of its maximum; a game whose system is
+    singular or not finite gets delta = 0"""
+    B, q = g.shape
+    delta = np.zeros((B, q))
+    for k in range(B):
+        d = np.diagonal(Hm[k])
+        if not (np.all(np.isfinite(Hm[k])) and np.all(np.isfinite(g[k])) and d.max() > 0):
+            continue
+        A = Hm[k] + lam[k] * np.diag(np.maximum(d, FIT_DIAG_FLOOR * d.max()))
+        try:
+            s = np.linalg.solve(A, -g[k])
+        except np.linalg.LinAlgError:
+            continue
+        if np.all(np.isfinite(s)):
+            delta[k] = s
+    return delta
 
 
 def inner_iteration(prob, LS_count, t_elap, Δ, k, l):

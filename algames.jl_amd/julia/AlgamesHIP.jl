@@ -885,6 +885,34 @@ function parameter_sensitivity(bp::BatchedGameProblem, wrt::Symbol; reg::Float64
     return X, status
 end
 
+"""
+    normal_equations(bp, cols, target, weight; reg=0.0, games=nothing) -> (H, g, loss, status)
+
+The normal equations of fitting parameters to an observed trajectory, reduced on the device (alg_kkt_normal_equations).  `cols` is a vector of
+`(wrt, index)` pairs, `wrt` a symbol of `parameter_sensitivity` and `index` the 1-based entry of that parameter vector: up to 63 distinct
+columns, kinds mixed in any order; column c is the unit column `parameter_sensitivity` returns for it.  `target` is S x B, the observed
+trajectory in the horizontal order of the Newton direction; `weight` is S (shared) or S x B, finite and >= 0.  With r = z - target over
+the S entries of `pdtraj` behind x_1, per game: `loss` = 1/2 sum w r^2, `g` = X' W r (q x B), `H` = X' W X (q x q x B, both triangles,
+symmetric bit for bit).  `status` (B): 0 where every column was solved.  `games = (first, count)` (0-based) restricts the call to those
+games (B = count).  No sensitivity column is downloaded.
+"""
+function normal_equations(bp::BatchedGameProblem, cols::AbstractVector, target::AbstractMatrix, weight::AbstractVecOrMat; reg::Float64=0.0, games=nothing)
+    ps = bp.probs[1].probsize
+    S = ps.S
+    g0, B = games === nothing ? (0, length(bp.probs)) : (Int(games[1]), Int(games[2]))
+    (g0 >= 0 && B >= 1 && g0 + B <= length(bp.probs)) || throw(ArgumentError("games = (first, count) must lie inside the batch of $(length(bp.probs))"))
+    q = length(cols)
+    1 <= q <= 63 || throw(ArgumentError("cols must name 1 ... 63 columns"))
+    size(target) == (S, B) || throw(ArgumentError("target must be $(S) x $(B)"))
+    (size(weight) == (S,) || size(weight) == (S, B)) || throw(ArgumentError("weight must be $(S) or $(S) x $(B)"))
+    cp = Int32[param_code(c[1]) for c in cols]; ci = Int32[Int(c[2]) - 1 for c in cols]
+    H = zeros(q, q, B); g = zeros(q, B); loss = zeros(B); status = zeros(Int32, B)
+    check(ccall((:alg_kkt_normal_equations, LIB), Cint,
+                (Ptr{Cvoid}, Float64, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                bp.h, reg, q, cp, ci, Array{Float64}(target), Array{Float64}(weight), ndims(weight) == 2 ? 1 : 0, g0, B, H, g, loss, status))
+    return H, g, loss, status
+end
+
 "Give the inspection entry points' device scratch (dense Jacobians, MPC state logs) back to the allocator."
 release_scratch!(bp::BatchedGameProblem) = check(ccall((:alg_release_scratch, LIB), Cint, (Ptr{Cvoid},), bp.h))
 

@@ -472,6 +472,32 @@ int alg_kkt_sensitivity(alg_handle* h, double reg, int32_t param,
                         int32_t first_game, int32_t n_games,
                         int32_t first_step, int32_t n_steps /* 0 = all N-1 */,
                         double* out /* n_games x ncol x (n_steps*b) */, int32_t* status /* n_games or NULL */);
+/* The normal equations of fitting parameters to an observed trajectory, reduced on the device: per game, with X_c = d z* / d theta of entry
+ * col_index[c] of parameter col_param[c] -- exactly the unit column alg_kkt_sensitivity returns for it (same J, reg, refinement gate and
+ * status rule; multipliers, penalties and active sets held) -- and r_e = z_e - target_e over the S entries of pdtraj behind x_1,
+ *   loss = 1/2 sum_e w_e r_e^2,   g_c = sum_e w_e X_ec r_e,   H_cd = sum_e w_e X_ec X_ed       (gradient and Gauss-Newton matrix of loss).
+ * Columns may mix parameter kinds in any order; the outputs follow the caller's order.  H comes back with both triangles, the lower a copy of
+ * the upper: symmetric bit for bit.  Every entry is one sum over e = 0, 1, ... in a fixed order inside one wavefront: results are
+ * bit-reproducible and do not depend on the game's place in the batch or in the range.  No column leaves the device: the download is H, g,
+ * loss and status.  status: per game the first status other than ALG_STATUS_OK among its columns, kinds in the order they first appear; a
+ * game whose status is not OK gets whatever the arithmetic gives in H, g and loss.
+ * ALG_ERR_ARG, with nothing changed, for a null handle, ncol < 1 or > ALG_NORMAL_MAX_COLS, an unknown kind, an index outside
+ * 0 .. alg_param_len(param) - 1, a (param, index) pair named twice, a null col_param, col_index, target, weight, H, g or loss, a non-finite
+ * target, a weight that is non-finite or negative, or a game range outside the batch; ALG_ERR_STATE, with nothing changed, where
+ * alg_kkt_sensitivity returns it (the ingredient of one of the kinds is not on the handle); the counts, pointers, ranges and columns are
+ * checked first, then the handle's ingredients, and only then are target and weight read.
+ * What the call leaves behind is what alg_kkt_sensitivity leaves behind: pdtraj, x0, multipliers, penalties, statistics, history and profiles
+ * are untouched; ALG_TRAJ_DELTA holds the last column solved; ALG_TRAJ_TRIAL is scratch (x_1 restored).  Uses the inspection scratch:
+ * n_games x ncol x S doubles of columns, per kind n_games x (its columns) x alg_param_len doubles of unit directions, and target, weight
+ * and the results -- cut the game range to bound it. */
+#define ALG_NORMAL_MAX_COLS 63
+int alg_kkt_normal_equations(alg_handle* h, double reg,
+                             int32_t ncol, const int32_t* col_param /* ncol x ALG_PARAM_* */, const int32_t* col_index /* ncol: 0 .. alg_param_len(param) - 1 */,
+                             const double* target /* n_games x S, horizontal order (the order of alg_kkt_solve's out) */,
+                             const double* weight /* S, or n_games x S when per_game_weight */, int32_t per_game_weight,
+                             int32_t first_game, int32_t n_games,
+                             double* H /* n_games x ncol x ncol */, double* g /* n_games x ncol */, double* loss /* n_games */,
+                             int32_t* status /* n_games or NULL */);
 /* line_search (solver_methods.jl:105-125) on the stored Δpdtraj. */
 int alg_line_search(alg_handle* h, double reg, const double* res_norm /*B*/, double* alpha /*B*/,
                     int32_t* j /*B*/);
