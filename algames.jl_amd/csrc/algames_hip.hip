@@ -1293,11 +1293,16 @@ int alg_residual(alg_handle* h, int32_t which, double reg, double* res, double* 
     return sync(H);
 }
 
+// the game range of a step-wise entry point must lie inside the batch
+static int game_range(const Params& p, const char* who, int32_t first_game, int32_t n_games) {
+    if (first_game < 0 || n_games < 1 || (long long)first_game + n_games > p.B) return fail(ALG_ERR_ARG, std::string(who) + ": game range outside the batch");
+    return ALG_OK;
+}
 int alg_residual_jacobian_games(alg_handle* h, double reg, int32_t first_game, int32_t n_games, double* jac) {
     if (!h || !jac) return fail(ALG_ERR_ARG, "alg_residual_jacobian: null argument");
     int rc = use_device(H); if (rc) return rc;
     const Params& p = H->pr;
-    if (first_game < 0 || n_games < 1 || (long long)first_game + n_games > p.B) return fail(ALG_ERR_ARG, "alg_residual_jacobian_games: game range outside the batch");
+    if ((rc = game_range(p, "alg_residual_jacobian_games", first_game, n_games))) return rc;
     const size_t bytes = sizeof(double) * (size_t)n_games * p.S * p.S;
     if ((rc = ensure_scratch(H, bytes))) return rc;
     LAUNCH_GRID(n_games, k_jacobian, H->pr, reg, (double*)H->d_scratch, (int)first_game);
@@ -1378,38 +1383,7 @@ int alg_newton_direction(alg_handle* h, double reg, double* delta, int32_t* stat
     return sync(H);
 }
 
-// J X = R for many right-hand sides (k_kkt_solve): [rhs | out | status] in the inspection scratch, one upload, one launch, one download
-int alg_kkt_solve(alg_handle* h, double reg, int32_t kind, int32_t nrhs, const double* rhs, int32_t first_game, int32_t n_games, double* out, int32_t* status) {
-    NEED_HANDLE("alg_kkt_solve");
-    const Params& p = H->pr;
-    if (kind != ALG_KKT_RHS_USER && kind != ALG_KKT_RHS_X0 && kind != ALG_KKT_RHS_XF) return fail(ALG_ERR_ARG, "alg_kkt_solve: kind must be ALG_KKT_RHS_USER, ALG_KKT_RHS_X0 or ALG_KKT_RHS_XF");
-    if (!out) return fail(ALG_ERR_ARG, "alg_kkt_solve: null out");
-    if (first_game < 0 || n_games < 1 || (long long)first_game + n_games > p.B) return fail(ALG_ERR_ARG, "alg_kkt_solve: game range outside the batch");
-    const bool user = kind == ALG_KKT_RHS_USER;
-    if (user) {
-        if (nrhs < 1) return fail(ALG_ERR_ARG, "alg_kkt_solve: ALG_KKT_RHS_USER needs nrhs >= 1");
-        if (!rhs) return fail(ALG_ERR_ARG, "alg_kkt_solve: ALG_KKT_RHS_USER needs rhs");
-    } else {
-        const int all = kind == ALG_KKT_RHS_X0 ? p.n : p.p * p.ni;
-        if (nrhs != 0 && nrhs != all) return fail(ALG_ERR_ARG, "alg_kkt_solve: nrhs must be n (ALG_KKT_RHS_X0) / p ni (ALG_KKT_RHS_XF), or 0 for all");
-        if (rhs) return fail(ALG_ERR_ARG, "alg_kkt_solve: rhs must be NULL unless ALG_KKT_RHS_USER");
-        nrhs = all;
-    }
-    const size_t cnt = (size_t)n_games * (size_t)nrhs * (size_t)p.S, b_col = sizeof(double) * cnt, b_rhs = user ? b_col : 0;
-    if (user) for (size_t e = 0; e < cnt; e++) if (!std::isfinite(rhs[e])) return fail(ALG_ERR_ARG, "alg_kkt_solve: game " + std::to_string(first_game + e / ((size_t)nrhs * p.S)) + ", column " + std::to_string(e / p.S % nrhs) + ": rhs must be finite");
-    int rc = use_device(H); if (rc) return rc;
-    if ((rc = ensure_scratch(H, b_rhs + b_col + sizeof(int) * (size_t)n_games))) return rc;
-    char* const d = (char*)H->d_scratch;
-    if (user && (rc = h2d(H, d, rhs, b_rhs))) return rc;
-    LAUNCH_GRID(n_games, k_kkt_solve, H->pr, reg, (int)kind, (int)nrhs, (const double*)(user ? d : nullptr), (int)first_game, (double*)(d + b_rhs), (int*)(d + b_rhs + b_col));
-    // (the columns come back in one copy; the status words, n_games ints behind them, go to a host buffer of their own)
-    if ((rc = d2h(H, out, d + b_rhs, b_col))) return rc;
-    if (status && (rc = d2h(H, status, d + b_rhs + b_col, sizeof(int) * (size_t)n_games))) return rc;
-    return ALG_OK;
-}
-
-// X = -J^-1 d res / d theta with the right-hand sides built on the device (k_kkt_sens): [dirs | out | status] in the inspection scratch, out
-// sized by the step slice
+// entries of a parameter kind of alg_kkt_sensitivity; -1: no such kind
 static int param_len(const Params& p, int32_t param) {
     switch (param) {
     case ALG_PARAM_X0: return p.n;
@@ -1421,6 +1395,60 @@ static int param_len(const Params& p, int32_t param) {
     }
     return -1;
 }
+// The KKT column kernel (k_kkt_sens) behind alg_kkt_solve, alg_kkt_sensitivity and alg_kkt_normal_equations.
+// kkt_launch: one launch on device pointers; d_in null = the ncol = len unit columns of param
+static int kkt_launch(Handle* h, double reg, int param, int ncol, int len, const double* d_in, int first_game, int n_games, int first_step, int n_steps, double* d_out,
+                      int* d_status) {
+    LAUNCH_GRID(n_games, k_kkt_sens, H->pr, reg, param, ncol, len, d_in, first_game, first_step, n_steps, d_out, d_status);
+    return ALG_OK;
+}
+// kkt_columns: a whole column call, [input | out | status] in the inspection scratch with out sized by the step slice: one upload (none
+// without input), one launch, one download of the columns; the status words, n_games ints behind them, go to a host buffer of their own
+static int kkt_columns(Handle* h, double reg, int param, int ncol, int len, const double* input, int first_game, int n_games, int first_step, int n_steps, double* out,
+                       int32_t* status) {
+    const Params& p = H->pr;
+    const size_t b_in = input ? sizeof(double) * (size_t)n_games * ncol * len : 0;
+    const size_t b_col = sizeof(double) * (size_t)n_games * ncol * n_steps * (size_t)(p.n + p.m + p.n * p.p), b_st = sizeof(int) * (size_t)n_games;
+    int rc = use_device(H); if (rc) return rc;
+    if ((rc = ensure_scratch(H, b_in + b_col + b_st))) return rc;
+    char* const d = (char*)H->d_scratch;
+    if (input && (rc = h2d(H, d, input, b_in))) return rc;
+    if ((rc = kkt_launch(H, reg, param, ncol, len, (const double*)(input ? d : nullptr), first_game, n_games, first_step, n_steps, (double*)(d + b_in), (int*)(d + b_in + b_col)))) return rc;
+    if ((rc = d2h(H, out, d + b_in, b_col))) return rc;
+    if (status && (rc = d2h(H, status, d + b_in + b_col, b_st))) return rc;
+    return ALG_OK;
+}
+// the numbers a parameter kind differentiates must be on the handle
+static int param_present(const Handle* hd, const char* who, int param) {
+    const Params& p = hd->pr;
+    const char* const missing = (param >= ALG_PARAM_XF && param <= ALG_PARAM_UF && !hd->lqr_set) ? "LQR data not set"
+                              : (param == ALG_PARAM_COLLISION_COST && !p.has_colcost) ? "no collision cost on the handle"
+                              : (param == ALG_PARAM_COLLISION_RADIUS && !p.has_colavoid) ? "no collision avoidance on the handle"
+                              : (param == ALG_PARAM_CONTROL_BOUND && !p.has_ctl) ? "no control bound on the handle" : nullptr;
+    return missing ? fail(ALG_ERR_STATE, std::string(who) + ": " + missing) : ALG_OK;
+}
+
+// J X = R for many right-hand sides: a column call over the full step range; X0 / XF are the unit columns of ALG_PARAM_X0 / ALG_PARAM_XF
+int alg_kkt_solve(alg_handle* h, double reg, int32_t kind, int32_t nrhs, const double* rhs, int32_t first_game, int32_t n_games, double* out, int32_t* status) {
+    NEED_HANDLE("alg_kkt_solve");
+    const Params& p = H->pr;
+    if (kind != ALG_KKT_RHS_USER && kind != ALG_KKT_RHS_X0 && kind != ALG_KKT_RHS_XF) return fail(ALG_ERR_ARG, "alg_kkt_solve: kind must be ALG_KKT_RHS_USER, ALG_KKT_RHS_X0 or ALG_KKT_RHS_XF");
+    if (!out) return fail(ALG_ERR_ARG, "alg_kkt_solve: null out");
+    int rc = game_range(p, "alg_kkt_solve", first_game, n_games); if (rc) return rc;
+    if (kind == ALG_KKT_RHS_USER) {
+        if (nrhs < 1) return fail(ALG_ERR_ARG, "alg_kkt_solve: ALG_KKT_RHS_USER needs nrhs >= 1");
+        if (!rhs) return fail(ALG_ERR_ARG, "alg_kkt_solve: ALG_KKT_RHS_USER needs rhs");
+        const size_t cnt = (size_t)n_games * (size_t)nrhs * (size_t)p.S;
+        for (size_t e = 0; e < cnt; e++) if (!std::isfinite(rhs[e])) return fail(ALG_ERR_ARG, "alg_kkt_solve: game " + std::to_string(first_game + e / ((size_t)nrhs * p.S)) + ", column " + std::to_string(e / p.S % nrhs) + ": rhs must be finite");
+        return kkt_columns(H, reg, SENS_RHS_USER, nrhs, p.S, rhs, first_game, n_games, 0, p.N - 1, out, status);
+    }
+    const int param = kind == ALG_KKT_RHS_X0 ? ALG_PARAM_X0 : ALG_PARAM_XF, all = param_len(p, param);
+    if (nrhs != 0 && nrhs != all) return fail(ALG_ERR_ARG, "alg_kkt_solve: nrhs must be n (ALG_KKT_RHS_X0) / p ni (ALG_KKT_RHS_XF), or 0 for all");
+    if (rhs) return fail(ALG_ERR_ARG, "alg_kkt_solve: rhs must be NULL unless ALG_KKT_RHS_USER");
+    return kkt_columns(H, reg, param, all, all, nullptr, first_game, n_games, 0, p.N - 1, out, status);
+}
+
+// X = -J^-1 d res / d theta with the right-hand sides built on the device: a column call over a step slice
 int alg_param_len(alg_handle* h, int32_t param, int32_t* len) {
     if (!h || !len) return fail(ALG_ERR_ARG, "alg_param_len: null argument");
     const int l = param_len(H->pr, param);
@@ -1434,30 +1462,16 @@ int alg_kkt_sensitivity(alg_handle* h, double reg, int32_t param, int32_t ndir, 
     const int len = param_len(p, param), K = p.N - 1;
     if (len < 0) return fail(ALG_ERR_ARG, "alg_kkt_sensitivity: unknown parameter " + std::to_string(param));
     if (!out) return fail(ALG_ERR_ARG, "alg_kkt_sensitivity: null out");
-    if (first_game < 0 || n_games < 1 || (long long)first_game + n_games > p.B) return fail(ALG_ERR_ARG, "alg_kkt_sensitivity: game range outside the batch");
+    int rc = game_range(p, "alg_kkt_sensitivity", first_game, n_games); if (rc) return rc;
     if (first_step < 0 || n_steps < 0 || (long long)first_step + n_steps > K || (n_steps == 0 && first_step != 0))
         return fail(ALG_ERR_ARG, "alg_kkt_sensitivity: step range outside 0 ... N - 2 (n_steps = 0 with first_step = 0: all steps)");
     if (n_steps == 0) n_steps = K;
     if (dirs ? ndir < 1 : ndir != 0) return fail(ALG_ERR_ARG, "alg_kkt_sensitivity: ndir must be >= 1 with dirs and 0 without");
-    const int ncol = dirs ? ndir : len;
     const size_t n_dir = dirs ? (size_t)n_games * ndir * len : 0;
     for (size_t e = 0; e < n_dir; e++)
         if (!std::isfinite(dirs[e])) return fail(ALG_ERR_ARG, "alg_kkt_sensitivity: game " + std::to_string(first_game + e / ((size_t)ndir * len)) + ", direction " + std::to_string(e / len % ndir) + ": dirs must be finite");
-    if (param >= ALG_PARAM_XF && param <= ALG_PARAM_UF && !H->lqr_set) return fail(ALG_ERR_STATE, "alg_kkt_sensitivity: LQR data not set");
-    if (param == ALG_PARAM_COLLISION_COST && !p.has_colcost) return fail(ALG_ERR_STATE, "alg_kkt_sensitivity: no collision cost on the handle");
-    if (param == ALG_PARAM_COLLISION_RADIUS && !p.has_colavoid) return fail(ALG_ERR_STATE, "alg_kkt_sensitivity: no collision avoidance on the handle");
-    if (param == ALG_PARAM_CONTROL_BOUND && !p.has_ctl) return fail(ALG_ERR_STATE, "alg_kkt_sensitivity: no control bound on the handle");
-    const size_t per = (size_t)n_steps * (size_t)(p.n + p.m + p.n * p.p);
-    const size_t b_dir = sizeof(double) * n_dir, b_col = sizeof(double) * (size_t)n_games * ncol * per;
-    int rc = use_device(H); if (rc) return rc;
-    if ((rc = ensure_scratch(H, b_dir + b_col + sizeof(int) * (size_t)n_games))) return rc;
-    char* const d = (char*)H->d_scratch;
-    if (dirs && (rc = h2d(H, d, dirs, b_dir))) return rc;
-    LAUNCH_GRID(n_games, k_kkt_sens, H->pr, reg, (int)param, (int)ncol, (int)len, (const double*)(dirs ? d : nullptr), (int)first_game, (int)first_step, (int)n_steps,
-                (double*)(d + b_dir), (int*)(d + b_dir + b_col));
-    if ((rc = d2h(H, out, d + b_dir, b_col))) return rc;
-    if (status && (rc = d2h(H, status, d + b_dir + b_col, sizeof(int) * (size_t)n_games))) return rc;
-    return ALG_OK;
+    if ((rc = param_present(H, "alg_kkt_sensitivity", param))) return rc;
+    return kkt_columns(H, reg, param, dirs ? ndir : len, len, dirs, first_game, n_games, first_step, n_steps, out, status);
 }
 
 // The normal equations of a fit (k_sens_gram over the columns of k_kkt_sens): the columns are grouped by parameter kind in the order the kinds
@@ -1473,7 +1487,7 @@ int alg_kkt_normal_equations(alg_handle* h, double reg, int32_t ncol, const int3
     if (ncol < 1 || ncol > ALG_NORMAL_MAX_COLS) return fail(ALG_ERR_ARG, "alg_kkt_normal_equations: ncol must be 1 ... " + std::to_string(ALG_NORMAL_MAX_COLS));
     if (!col_param || !col_index) return fail(ALG_ERR_ARG, "alg_kkt_normal_equations: null col_param or col_index");
     if (!target || !weight || !Hout || !gout || !loss) return fail(ALG_ERR_ARG, "alg_kkt_normal_equations: null target, weight, H, g or loss");
-    if (first_game < 0 || n_games < 1 || (long long)first_game + n_games > p.B) return fail(ALG_ERR_ARG, "alg_kkt_normal_equations: game range outside the batch");
+    int rc = game_range(p, "alg_kkt_normal_equations", first_game, n_games); if (rc) return rc;
     struct Group { int param, len; std::vector<int> idx; };
     std::vector<Group> groups;
     int gof[NKIND], group_of[ALG_NORMAL_MAX_COLS], pos_of[ALG_NORMAL_MAX_COLS];
@@ -1488,12 +1502,8 @@ int alg_kkt_normal_equations(alg_handle* h, double reg, int32_t ncol, const int3
         group_of[c] = gof[col_param[c]]; pos_of[c] = (int)groups[group_of[c]].idx.size();
         groups[group_of[c]].idx.push_back(col_index[c]);
     }
-    for (const Group& gr : groups) {
-        if (gr.param >= ALG_PARAM_XF && gr.param <= ALG_PARAM_UF && !H->lqr_set) return fail(ALG_ERR_STATE, "alg_kkt_normal_equations: LQR data not set");
-        if (gr.param == ALG_PARAM_COLLISION_COST && !p.has_colcost) return fail(ALG_ERR_STATE, "alg_kkt_normal_equations: no collision cost on the handle");
-        if (gr.param == ALG_PARAM_COLLISION_RADIUS && !p.has_colavoid) return fail(ALG_ERR_STATE, "alg_kkt_normal_equations: no collision avoidance on the handle");
-        if (gr.param == ALG_PARAM_CONTROL_BOUND && !p.has_ctl) return fail(ALG_ERR_STATE, "alg_kkt_normal_equations: no control bound on the handle");
-    }
+    for (const Group& gr : groups)
+        if ((rc = param_present(H, "alg_kkt_normal_equations", gr.param))) return rc;
     const size_t S = (size_t)p.S, n_tgt = (size_t)n_games * S, n_wt = per_game_weight ? n_tgt : S;
     for (size_t e = 0; e < n_tgt; e++)
         if (!std::isfinite(target[e])) return fail(ALG_ERR_ARG, "alg_kkt_normal_equations: game " + std::to_string(first_game + e / S) + ": target must be finite");
@@ -1519,7 +1529,7 @@ int alg_kkt_normal_equations(alg_handle* h, double reg, int32_t ncol, const int3
         double* const dv = (double*)(up.data() + o_dir[k]);
         for (int g = 0; g < n_games; g++) dv[((size_t)g * cols_k + pos_of[c]) * groups[k].len + col_index[c]] = 1.0;
     }
-    int rc = use_device(H); if (rc) return rc;
+    if ((rc = use_device(H))) return rc;
     if ((rc = ensure_scratch(H, total))) return rc;
     char* const d = (char*)H->d_scratch;
     if ((rc = h2d(H, d, up.data(), b_up))) return rc;
@@ -1527,8 +1537,8 @@ int alg_kkt_normal_equations(alg_handle* h, double reg, int32_t ncol, const int3
     if ((rc = h2d(H, d + o_wt, weight, sizeof(double) * n_wt))) return rc;
     for (int k = 0; k < ng; k++) {
         const Group& gr = groups[k];
-        LAUNCH_GRID(n_games, k_kkt_sens, H->pr, reg, gr.param, (int)gr.idx.size(), gr.len, (const double*)(d + o_dir[k]), (int)first_game, 0, p.N - 1,
-                    (double*)(d + o_seg[k]), (int*)(d + o_gst + b_st * k));
+        if ((rc = kkt_launch(H, reg, gr.param, (int)gr.idx.size(), gr.len, (const double*)(d + o_dir[k]), first_game, n_games, 0, p.N - 1, (double*)(d + o_seg[k]),
+                             (int*)(d + o_gst + b_st * k)))) return rc;
     }
     hipLaunchKernelGGL(k_sens_gram, dim3(n_games), dim3(GRAM_WAVES * WAVE), 0, H->stream, H->pr, (const long long*)d, (const double*)(d + o_col), (const double*)(d + o_tgt),
                        (const double*)(d + o_wt), (int)(per_game_weight != 0), q, (int)first_game, ng, (const int*)(d + o_gst), (double*)(d + o_H), (double*)(d + o_g),

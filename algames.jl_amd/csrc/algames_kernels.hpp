@@ -505,96 +505,11 @@ __global__ void __launch_bounds__(C::NT, mpc_loop_wpe<C>) k_mpc_loop_sched(Param
     }
 }
 
-// KKT solves with many right-hand sides (alg_kkt_solve): one assemble pass at pdtraj, then per column the structured
-// elimination of refined_direction on a right-hand side written into the three right-hand-side blocks of the step records (Rec::RX / RU / RD) --
-// the blocks the refinement's correction solves already rewrite (dir_urow_residual<..., WRITE>).  The sweeps solve J d = -record, so:
-//   ALG_KKT_RHS_USER  the caller's column (vertical order of alg_residual) is stored negated: J X = R
-//   ALG_KKT_RHS_X0    column c: rd of step 0 = A_0[:, c] (A_entry on the coefficient block of record 0), zero elsewhere: X = -J^-1 d res / d x_1
-//   ALG_KKT_RHS_XF    column (i, a), the xf order of alg_set_lqr: rx of player i at i's own state a (joint index a P + i) = -w_k Q_i[a] in every
-//                     step (w_k: the stage / terminal weight jacobian_dense hands to qhat_entry; d res / d xf = -w Q), zero elsewhere:
-//                     X = -J^-1 d res / d x_f
-// A correction pass zeroes rx / rd and overwrites ru, so every column rewrites all three blocks of all N - 1 steps.
-template <class C>
-__device__ void kkt_load_rhs(CPR pr0, const Game& G0, const int kind, const int col, const double* const rhs) {
-    CPR pr = phase_params(pr0);
-    const Game G = G0.fresh();
-    constexpr int n = C::n, m = C::m, P = C::P;
-    using R = Rec<C>;
-    const int N = phase_int(pr.N), tid = phase_lane();
-    double* __restrict__ recs = G.rec(pr);
-    if (kind == ALG_KKT_RHS_USER) {
-        const double* __restrict__ src = as_global(rhs);
-        for (int e = tid; e < (N - 1) * P * n; e += C::NT) { const int k = e / (P * n), q = e % (P * n); gst(recs, k * R::LEN + R::RX + q, -gld(src, vx<C>(N, q / n, k) + q % n)); }
-        for (int e = tid; e < (N - 1) * m; e += C::NT) { const int k = e / m, c = e % m; gst(recs, k * R::LEN + R::RU + c, -gld(src, vu<C>(N, c % P, k) + c / P)); }
-        for (int e = tid; e < (N - 1) * n; e += C::NT) { const int k = e / n, r = e % n; gst(recs, k * R::LEN + R::RD + r, -gld(src, vd<C>(N, k) + r)); }
-        return;
-    }
-    const double dt = phase_f64(pr.dt);
-    // XF: the one non-zero rx entry of a step and its value up to the step's weight
-    const int xi = col / C::ni, xa = col % C::ni, xq = xi * n + xa * P + xi;
-    const double qv = kind == ALG_KKT_RHS_XF ? G.Qd(pr)[xi * C::ni + xa] : 0.0;
-    for (int e = tid; e < (N - 1) * P * n; e += C::NT) {
-        const int k = e / (P * n), q = e % (P * n);
-        const double w = (k + 1 < N - 1) ? dt : 1.0;
-        gst(recs, k * R::LEN + R::RX + q, (kind == ALG_KKT_RHS_XF && q == xq) ? -(w * qv) : 0.0);
-    }
-    for (int e = tid; e < (N - 1) * m; e += C::NT) gst(recs, (e / m) * R::LEN + R::RU + e % m, 0.0);
-    for (int e = tid; e < (N - 1) * n; e += C::NT) {
-        const int k = e / n, r = e % n;
-        gst(recs, k * R::LEN + R::RD + r, (kind == ALG_KKT_RHS_X0 && k == 0) ? A_entry<C>(recs + R::COEF, dt, r, col) : 0.0);
-    }
-}
-// the column's solution: the S doubles behind the x_1 slot of the delta buffer, horizontal order
-template <class C>
-__device__ void kkt_store_column(CPR pr0, const Game& G0, double* const dst) {
-    CPR pr = phase_params(pr0);
-    const Game G = G0.fresh();
-    const int S = phase_int(pr.S), tid = phase_lane();
-    const double* __restrict__ dz = G.z(2);
-    double* __restrict__ o = as_global(dst);
-    for (int e = tid; e < S; e += C::NT) gst(o, e, gld(dz, C::n + e));
-}
-// One wavefront per game (always: a step-wise entry point), games g0 .. g0 + gridDim.x - 1; rhs / out hold gridDim.x x nrhs columns of S doubles,
-// status gridDim.x entries: the first non-OK status of the game's columns.  Only the column counter and that status live across the columns; the
-// call's own arguments are re-read from the kernel-argument segment where they are used, like k_mpc_loop's.
-struct KktArgs { Params pr; double reg; int kind, nrhs; const double* rhs; int g0; double* out; int* status; };
-template <class C>
-__global__ void __launch_bounds__(WAVE, C::WPE) k_kkt_solve(Params pr_arg, double reg_arg, int kind_arg, int nrhs_arg, const double* rhs_arg, int g0_arg, double* out_arg,
-                                                            int* status_arg) {
-    __shared__ Lds<C> L;
-    CPR pr = kernel_params();
-#if defined(__HIP_DEVICE_COMPILE__)
-    const ALG_AS4 KktArgs& ka = *(const ALG_AS4 KktArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-#else
-    const KktArgs& ka = *(const KktArgs*)nullptr;      // host pass: never executed
-#endif
-    auto kq = [&]() -> const ALG_AS4 KktArgs& { return *(const ALG_AS4 KktArgs*)uniform_u64((unsigned long long)&ka); };
-    const int gl = blockIdx.x;
-    Game G = game_view(pr, gl + kq().g0);
-    ResOut ro;
-    assemble_pass<C, 1>(pr, G, L.a, 0, -1, 0.0, kq().reg, ro);
-    __syncthreads();
-    int worst = ALG_STATUS_OK;
-    for (int r = 0; r < kq().nrhs; r++) {
-        const size_t at = ((size_t)phase_int(gl) * kq().nrhs + r) * (size_t)phase_int(pr.S);
-        const double* const src = kq().rhs;
-        kkt_load_rhs<C>(pr, G, kq().kind, r, src ? src + at : nullptr);
-        game_sync();
-        const int st = refined_direction<C, false, false>(pr, G, L, kq().reg, -1, nullptr);
-        if (worst == ALG_STATUS_OK) worst = st;
-        game_sync();
-        kkt_store_column<C>(pr, G, kq().out + ((size_t)phase_int(gl) * kq().nrhs + r) * (size_t)phase_int(pr.S));
-        game_sync();
-    }
-    int* const so = kq().status;
-    if (so && phase_lane() == 0) as_global(so)[phase_int(gl)] = worst;
-}
-
 // Players' costs of a plan and of a closed-loop run (k_player_cost, k_closed_loop_cost)
 #include "algames_cost.hpp"
 // Constraint values of a plan and of a closed-loop run, row by row (k_con_values, k_closed_loop_con)
 #include "algames_con.hpp"
-// Equilibrium sensitivities to objective and constraint parameters (k_kkt_sens, the sibling of k_kkt_solve)
+// The KKT column kernel: solves with many right-hand sides and parameter sensitivities (k_kkt_sens)
 #include "algames_sens.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -782,10 +697,8 @@ __global__ void __launch_bounds__(WAVE, C::WPE) k_kkt_solve(Params pr_arg, doubl
 #define ALG_DEFINE_PLANT(M, P, D, E) ALG_INSTANTIATE_PLANT(template, M, P, D, E)
 #define ALG_DECLARE_PLANT(M, P, D, E) ALG_INSTANTIATE_PLANT(extern template, M, P, D, E)
 #define ALG_DECLARE_SCHED_MW(M, P, D, E, W) ALG_INSTANTIATE_SCHED_MW(extern template, M, P, D, E, W)
-// The KKT solves with many right-hand sides (k_kkt_solve) and their parameter-sensitivity siblings (k_kkt_sens): one of each per configuration
-// that has a k_direction, in units of their own
+// The KKT column kernel (k_kkt_sens): one per configuration that has a k_direction, in units of their own
 #define ALG_INSTANTIATE_KKT(PREFIX, M, P, D, E)                                                                            \
-    PREFIX __global__ void k_kkt_solve<Cfg<M, P, D, E>>(Params, double, int, int, const double*, int, double*, int*);      \
     PREFIX __global__ void k_kkt_sens<Cfg<M, P, D, E>>(Params, double, int, int, int, const double*, int, int, int, double*, int*);
 #define ALG_DEFINE_KKT(M, P, D, E) ALG_INSTANTIATE_KKT(template, M, P, D, E)
 #define ALG_DECLARE_KKT(M, P, D, E) ALG_INSTANTIATE_KKT(extern template, M, P, D, E)

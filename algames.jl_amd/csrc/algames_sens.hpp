@@ -1,14 +1,22 @@
-// algames_sens.hpp -- equilibrium sensitivities to objective and constraint parameters (alg_kkt_sensitivity).
-// k_kkt_sens<C> is the sibling of k_kkt_solve<C>: one assemble pass at pdtraj, then per column a loader, the structured elimination of
-// refined_direction and a store.  What differs from k_kkt_solve is the loader and the store:
-//   the loader writes sum_c v_c d res / d theta_c into the three right-hand-side blocks (Rec::RX / RU / RD) of all N - 1 steps, evaluated at
-//   pdtraj with the game's multipliers and penalties and the numbers the game was assembled with (per-game LQR data, the game's scenario
-//   block or the handle's values, through ALG_SCEN_AT) -- the sweeps solve J d = -record, so the column is X v = -J^-1 (d res / d theta) v.
-//   A unit column is v = e_c, formed without a direction in memory.
-//   the store copies the blocks of the requested steps only: out holds n_steps * b doubles per column.
-// The terms, row by row of the oracle's residual (w_k = dt, 1 on the terminal step; joint state index s = a P + j is entry a of player j):
-//   X0   rd of step 0:            A_0[:, c]                                              (kkt_load_rhs' ALG_KKT_RHS_X0)
-//   XF   rx_i[a P + i]:           -w_k Q_i[a]                                            (... ALG_KKT_RHS_XF)
+// algames_sens.hpp -- the KKT column kernel: J X = R for many right-hand sides, answered on the device.
+// k_kkt_sens<C> is the one kernel behind alg_kkt_solve, alg_kkt_sensitivity and, through per-kind launches, alg_kkt_normal_equations: one
+// assemble pass at pdtraj, then per column a loader, the structured elimination of refined_direction and a store.
+//   the loader writes the column's right-hand side into the three right-hand-side blocks of the step records (Rec::RX / RU / RD) of all
+//   N - 1 steps -- the blocks the refinement's correction solves already rewrite (dir_urow_residual<..., WRITE>).  The sweeps solve
+//   J d = -record, so a column of J X = R is stored negated and a column of X = -J^-1 (d res / d theta) v as sum_c v_c d res / d theta_c.
+//   the store copies the blocks of the requested steps only: out holds n_steps * b doubles per column (all N - 1 steps: the S doubles behind
+//   the x_1 slot of the delta buffer, horizontal order).
+// The right-hand-side kinds (the param argument):
+//   SENS_RHS_USER  the caller's column of S doubles, in the vertical order of alg_residual (alg_kkt_solve's ALG_KKT_RHS_USER): J X = R.  A
+//                  plain sign flip per entry: with R = -res the records hold what k_direction's hold, bit for bit.
+//   ALG_PARAM_*    d res / d theta built here, evaluated at pdtraj with the game's multipliers and penalties and the numbers the game was
+//                  assembled with (per-game LQR data, the game's scenario block or the handle's values, through ALG_SCEN_AT).  A unit column
+//                  is v = e_c, formed without a direction in memory.  ALG_KKT_RHS_X0 / XF of alg_kkt_solve are the unit columns of
+//                  ALG_PARAM_X0 / XF.
+// The terms, row by row of the oracle's residual (w_k = dt, 1 on the terminal step -- the stage / terminal weight jacobian_dense hands to
+// qhat_entry; joint state index s = a P + j is entry a of player j):
+//   X0   rd of step 0:            A_0[:, c]  (A_entry on the coefficient block of record 0)
+//   XF   rx_i[a P + i]:           -w_k Q_i[a]  (the xf order of alg_set_lqr)
 //   Q    rx_i[a P + i]:           w_k (x - xf_i[a])
 //   R    ru[c]:                   dt (u - uf)                  UF  ru[c]: -dt R
 //   COLLISION_COST  rx_i at the positions of i and j, pairs with r_i - |d| > 0 only, g_a = mu_i (r_i (eps + d_a) / (eps_n + |d|) - d_a):
@@ -20,6 +28,8 @@
 // correction pass of the refinement zeroes rx / rd and overwrites ru.  No LDS beyond k_direction's.
 #pragma once
 #include "algames_device.hpp"
+
+constexpr int SENS_RHS_USER = -1;           // internal: not an ALG_PARAM_* of the C ABI (alg_kkt_sensitivity and alg_param_len refuse it)
 
 template <class C>
 __device__ void sens_load_rhs(CPR pr0, const Game& G0, const int param, const int col, const double* const dir) {
@@ -38,6 +48,7 @@ __device__ void sens_load_rhs(CPR pr0, const Game& G0, const int param, const in
         const int k = e / (P * n), q = e % (P * n), i = q / n, s = q % n, a = s / P, j = s % P;
         const double w = (k + 1 < N - 1) ? dt : 1.0;
         const double* __restrict__ x = z + n + hx<C>(k);
+        if (param == SENS_RHS_USER) { gst(recs, k * R::LEN + R::RX + q, -gld(dv, vx<C>(N, i, k) + s)); continue; }
         double r = 0.0;
         if (param == ALG_PARAM_XF) {
             if (j == i) r = -(w * gld(G.Qd(pr), i * ni + a)) * v(i * ni + a);
@@ -83,6 +94,7 @@ __device__ void sens_load_rhs(CPR pr0, const Game& G0, const int param, const in
     // ru: rows opt_i,u_{i,k}, joint control index c = jc P + i
     for (int e = tid; e < (N - 1) * m; e += C::NT) {
         const int k = e / m, c = e % m, i = c % P, jc = c / P, pi = i * mi + jc;
+        if (param == SENS_RHS_USER) { gst(recs, k * R::LEN + R::RU + c, -gld(dv, vu<C>(N, i, k) + jc)); continue; }
         double r = 0.0;
         if (param == ALG_PARAM_R || param == ALG_PARAM_UF || param == ALG_PARAM_CONTROL_BOUND) {
             const double u = gld(z, n + hu<C>(k, i) + jc);
@@ -101,6 +113,7 @@ __device__ void sens_load_rhs(CPR pr0, const Game& G0, const int param, const in
     // rd: the dynamics rows; x_1 enters step 0 alone
     for (int e = tid; e < (N - 1) * n; e += C::NT) {
         const int k = e / n, row = e % n;
+        if (param == SENS_RHS_USER) { gst(recs, k * R::LEN + R::RD + row, -gld(dv, vd<C>(N, k) + row)); continue; }
         double r = 0.0;
         if (param == ALG_PARAM_X0 && k == 0) {
             if (!dir) r = A_entry<C>(recs + R::COEF, dt, row, col);
@@ -118,9 +131,9 @@ __device__ void sens_store_column(CPR pr0, const Game& G0, double* const dst, co
     double* __restrict__ o = as_global(dst);
     for (int e = tid; e < cnt; e += C::NT) gst(o, e, gld(dz, e));
 }
-// One wavefront per game, games g0 .. g0 + gridDim.x - 1.  dirs: gridDim.x x ncol x len, or null: ncol = len unit columns.  out: gridDim.x x
+// One wavefront per game, games g0 .. g0 + gridDim.x - 1.  dirs: gridDim.x x ncol x len, or null: ncol = len unit columns (SENS_RHS_USER: the columns themselves, len = S).  out: gridDim.x x
 // ncol x (nstep b); status: the first non-OK status of the game's columns.  Arguments are re-read from the kernel-argument segment where
-// they are used, like k_kkt_solve's.
+// they are used, like k_mpc_loop's; only the column counter and the status live across the columns.
 struct SensArgs { Params pr; double reg; int param, ncol, len; const double* dirs; int g0, step0, nstep; double* out; int* status; };
 template <class C>
 __global__ void __launch_bounds__(WAVE, C::WPE) k_kkt_sens(Params pr_arg, double reg_arg, int param_arg, int ncol_arg, int len_arg, const double* dirs_arg, int g0_arg,

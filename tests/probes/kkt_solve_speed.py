@@ -6,10 +6,11 @@
 HIP events on the launch stream (torch events on a torch stream handed to the handle), WARM warm-up calls, then ROUNDS x CALLS calls; median
 over the rounds and every round's figure are printed.  alg_kkt_solve is a synchronous call -- launch, then the download of its columns (12
 columns x 4096 games x 2106 doubles = 828 MB at C2) -- so the events around it measure kernel + download; the kernel alone is what a kernel trace
-of this script shows (rocprofv3 --kernel-trace --stats -- python tests/probes/kkt_solve_speed.py: k_kkt_solve / k_direction rows).
+of this script shows (rocprofv3 --kernel-trace --stats -- python tests/probes/kkt_solve_speed.py: k_kkt_sens / k_direction rows; in the
+trace the X0 calls come first, then the USER calls -- a library from before the one column kernel shows them as k_kkt_solve).
 alg_newton_direction is called with NULL outputs through the raw ABI: launch and synchronisation only, its event time is its kernel time.
-  --parent   only the rows a library without alg_kkt_solve has (k_direction, newton_solve): run it on a build of the parent commit, alternated
-             with runs of this build by the caller."""
+  --parent   the library is a build of the parent commit, alternated with runs of this build by the caller: k_direction, newton_solve and, when
+             the library exports alg_kkt_solve, its X0 and USER rows; not the host route."""
 import argparse
 import os
 import sys
@@ -75,7 +76,7 @@ def main():
     say("# 12 x k_direction = %.3f ms" % (12 * d_med))
     s_med, s_ms = timed(stream, lambda: b.newton_solve_async(init=True, game_id0=0), calls=2)
     row("newton_solve of the batch", s_med, s_ms)
-    if a.parent:
+    if "kkt_solve" in b.lib.absent:
         return
     b.newton_solve(init=True, game_id0=0)
     X = np.empty((B, b.n, b.S)); st = np.empty(B, dtype=np.int32)
@@ -84,6 +85,14 @@ def main():
     row("alg_kkt_solve X0, %d columns (+ %.0f MB download)" % (b.n, X.nbytes / 1e6), k_med, k_ms)
     assert np.all(st == 0)
     say("# X0 call / (12 x k_direction) = %.3f ; X0 call / newton_solve = %.3f" % (k_med / (12 * d_med), k_med / s_med))
+    R = np.random.default_rng(0).uniform(-1.0, 1.0, (B, 12, b.S))
+    XU = np.empty_like(R)
+    rp, up = R.ctypes.data_as(alg._abi._D), XU.ctypes.data_as(alg._abi._D)
+    u_med, u_ms = timed(stream, lambda: b.lib.check(b.lib.kkt_solve(b.h, 0.0, alg.ALG_KKT_RHS_USER, 12, rp, 0, B, up, sp)), calls=1)
+    row("alg_kkt_solve USER, 12 columns (+ %.0f MB upload, %.0f MB download)" % (R.nbytes / 1e6, XU.nbytes / 1e6), u_med, u_ms)
+    assert np.all(st == 0)
+    if a.parent:
+        return
     # the host route as context: dense Jacobians to the host, LAPACK there
     G = a.lapack_games
     t0 = time.perf_counter()

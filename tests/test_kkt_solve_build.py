@@ -1,6 +1,6 @@
 """CPU-side checks of the KKT solves with many right-hand sides (alg_kkt_solve): the C ABI declares and exports the entry point, the Python
-layers refuse wrong arguments before any device call, every configuration that has a k_direction<...> kernel has its k_kkt_solve<...> with the
-resources of that k_direction, and the solver kernels k_newton_solve* / k_mpc_loop* keep the metadata they had before the feature, entry for
+layers refuse wrong arguments before any device call, every configuration that has a k_direction<...> kernel has its KKT column kernel k_kkt_sens<...> (the one
+kernel of alg_kkt_solve, alg_kkt_sensitivity and alg_kkt_normal_equations) with the resources of that k_direction, and the solver kernels k_newton_solve* / k_mpc_loop* keep the metadata they had before the feature, entry for
 entry (tests/golden/solver_kernel_resources_parent.json: a build of the commit before it).  No GPU needed."""
 import ctypes
 import importlib.util
@@ -99,15 +99,17 @@ def test_sensitivity_accessors_follow_the_horizontal_index_maps(alg):
 
 
 def test_every_direction_kernel_has_its_kkt_solve_with_the_same_resources(alg):
-    """k_kkt_solve<C> exists for every Cfg that has a k_direction<C> (base, EXT, the block-reading twins, the dense-direction configurations) and
-    nowhere else (no team shape); it spills no VGPR, uses scratch only where its k_direction does, and has that kernel's LDS size."""
+    """k_kkt_sens<C>, the column kernel of all three KKT entry points, exists for every Cfg that has a k_direction<C> (base, EXT, the
+    block-reading twins, the dense-direction configurations) and nowhere else (no team shape); it spills no VGPR, uses scratch only where its
+    k_direction does, and has that kernel's LDS size: the loader and the sliced store add none.  No k_kkt_solve<C> is left beside it."""
     res = _resources(alg)
     dirs = {k[len("k_direction"):]: v for k, v in res.items() if k.startswith("k_direction<")}
-    kkt = {k[len("k_kkt_solve"):]: v for k, v in res.items() if k.startswith("k_kkt_solve<")}
+    kkt = {k[len("k_kkt_sens"):]: v for k, v in res.items() if k.startswith("k_kkt_sens<")}
     assert len(dirs) >= 79 and sorted(kkt) == sorted(dirs)
+    assert not [k for k in res if k.startswith("k_kkt_solve<")]
     for c, d in sorted(dirs.items()):
         v = kkt[c]
-        print("k_kkt_solve%-24s vgpr %3d (direction %3d) sgpr %3d sgpr_spill %3d (%3d) scratch %4d (%4d) lds %6d" % (
+        print("k_kkt_sens%-24s vgpr %3d (direction %3d) sgpr %3d sgpr_spill %3d (%3d) scratch %4d (%4d) lds %6d" % (
             c, v["vgpr"], d["vgpr"], v["sgpr"], v["sgpr_spill"], d["sgpr_spill"], v["scratch"], d["scratch"], v["lds"]))
         assert v["vgpr_spill"] == 0, (c, v)
         assert v["scratch"] == 0 or d["scratch"] > 0, (c, v, d)

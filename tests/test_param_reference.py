@@ -1,5 +1,5 @@
 """The preconditions of tests/test_gpu_param_sensitivity.py, on the CPU: the REFERENCE of the parameter sensitivities (oracle + numpy), the C ABI
-and the Python argument checks of alg_kkt_sensitivity, and the metadata of its kernels.  No GPU needed.
+and the Python argument checks of alg_kkt_sensitivity (the metadata of its kernel: tests/test_kkt_solve_build.py).  No GPU needed.
 
   * the right-hand sides R = -d res / d theta written down on the host (param_reference.analytic_rhs) equal central differences of the
     oracle's residual, for xf and every new parameter, on the random data of the parity tests (pair_problem) and on solved family games, all
@@ -18,7 +18,6 @@ and the Python argument checks of alg_kkt_sensitivity, and the metadata of its k
   * on the double integrator (3 players N = 6, 2 players N = 4) the reference X = J^-1 R of one column per new parameter is the derivative of
     the polished root, as test_kkt_sensitivity_family._x0_gap shows for x0: 1e-7 max |X|."""
 import ctypes
-import importlib.util
 import os
 import re
 
@@ -33,7 +32,6 @@ from test_kkt_sensitivity_family import _as_product, _make, _polish
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "algames_hip.h")
 CHECKED = ("xf",) + PR.NEW
-_RES = {}
 
 
 @pytest.mark.parametrize("name", list(K.SHAPES))
@@ -195,25 +193,3 @@ def test_sliced_sensitivity_accessors(alg):
         with pytest.raises(IndexError):
             bad()
 
-
-def _resources(alg):
-    if not _RES:
-        spec = importlib.util.spec_from_file_location("_resources", os.path.join(ROOT, "algames.jl_amd", "_resources.py"))
-        mod = importlib.util.module_from_spec(spec); spec.loader.exec_module(mod)
-        _RES.update(mod.kernel_resources(_lib_path(alg)))
-    return _RES
-
-
-def test_every_kkt_solve_has_its_sensitivity_sibling_with_the_directions_lds(alg):
-    """k_kkt_sens<C> exists exactly where k_kkt_solve<C> does; it spills no VGPR, uses scratch only where its k_direction does, and has that
-    kernel's LDS size: the loader and the sliced store add none."""
-    res = _resources(alg)
-    dirs = {k[len("k_direction"):]: v for k, v in res.items() if k.startswith("k_direction<")}
-    kkt = {k[len("k_kkt_solve"):] for k in res if k.startswith("k_kkt_solve<")}
-    sens = {k[len("k_kkt_sens"):]: v for k, v in res.items() if k.startswith("k_kkt_sens<")}
-    assert len(kkt) >= 79 and sorted(sens) == sorted(kkt)
-    for c, v in sorted(sens.items()):
-        d = dirs[c]
-        assert v["vgpr_spill"] == 0, (c, v)
-        assert v["scratch"] == 0 or d["scratch"] > 0, (c, v, d)
-        assert v["lds"] == d["lds"], (c, v, d)
