@@ -9,7 +9,11 @@ its batch's numbers in `o._num`.
 
 Central differences re-assemble the oracle batch with one entry of theta moved by +-h (all games of the batch at once: the numbers of the
 constraints are shared by a batch, per-game LQR data moves the same entry of every game) and restore the batch afterwards.  The pair table is
-rebuilt pair by pair (add_collision_avoidance_pair), which is the only way the oracle takes a radius of one ordered pair."""
+rebuilt pair by pair (add_collision_avoidance_pair), which is the only way the oracle takes a radius of one ordered pair.
+
+A handle need not carry every ingredient (one player has no collision terms), and its pair table may have been built pair by pair
+(add_collision_avoidance_pair: a partial, asymmetric table).  `carried` names the parameters a handle has; `numbers` leaves an ingredient
+that was never added out, and gives the pair table with the mask `on` of the ordered pairs that exist (a never-added pair: radius 0, off)."""
 import contextlib
 
 import numpy as np
@@ -27,13 +31,17 @@ EPS = 1e-10                                        # the eps of the CollisionCos
 _SETTERS = ("set_lqr", "add_collision_cost", "add_collision_avoidance", "add_control_bound")
 
 
+PAIRS = "add_collision_avoidance_pair"            # key of o._num of a table built pair by pair: ((p, p) radii, 0 where never added,)
+
+
 @contextlib.contextmanager
 def recorded():
     """while active, every Batch (oracle batches included) keeps the arguments of its last set_lqr / add_collision_cost /
-    add_collision_avoidance / add_control_bound in self._num"""
+    add_collision_avoidance / add_control_bound in self._num, and the ordered pairs of add_collision_avoidance_pair as one (p, p) table under
+    PAIRS (the all-pairs form and the pair-by-pair form replace each other, as on the handle)"""
     import algames_jl_amd as A
     names = _SETTERS + ("add_spherical_collision_avoidance",)
-    orig = {k: getattr(A.Batch, k) for k in names}
+    orig = {k: getattr(A.Batch, k) for k in names + (PAIRS,)}
 
     def wrap(k):
         def f(self, *a):
@@ -42,14 +50,25 @@ def recorded():
             num["add_collision_avoidance" if k.startswith("add_spherical") else k] = tuple(np.array(v, dtype=np.float64) for v in a)
             if k.endswith("collision_avoidance"):
                 self._dims = 3 if k.startswith("add_spherical") else 2
+                num.pop(PAIRS, None)
             return orig[k](self, *a)
         return f
+
+    def pair(self, i, j, radius, spherical=False):
+        num = self.__dict__.setdefault("_num", {})
+        num.pop("add_collision_avoidance", None)
+        tab = num.get(PAIRS, (np.zeros((self.p, self.p)),))[0].copy()
+        tab[i, j] = radius
+        num[PAIRS] = (tab,)
+        self._dims = 3 if spherical else 2
+        return orig[PAIRS](self, i, j, radius, spherical=spherical)
     for k in names:
         setattr(A.Batch, k, wrap(k))
+    setattr(A.Batch, PAIRS, pair)
     try:
         yield
     finally:
-        for k in names:
+        for k in names + (PAIRS,):
             setattr(A.Batch, k, orig[k])
 
 
@@ -63,16 +82,45 @@ def family_problem(make, name, N, B=4):
         return K.family_problem(make, name, N, B=B)
 
 
+def _pair_table(o, num):
+    """(pair (p, p), on (p, p) bool) of the recorded collision avoidance, or None: r_i + r_j on every ordered pair of the all-pairs form, the
+    recorded radii of the pairs that were added one by one; the diagonal and a never-added pair are 0 and off"""
+    p = o.p
+    if "add_collision_avoidance" in num:
+        r = np.broadcast_to(num["add_collision_avoidance"][0], (p,))
+        return (r[:, None] + r[None, :]) * (1 - np.eye(p)), ~np.eye(p, dtype=bool)
+    if PAIRS in num:
+        tab = num[PAIRS][0] * (1 - np.eye(p))
+        return tab, tab > 0
+    return None
+
+
+INGREDIENT = {"collision_cost": "add_collision_cost", "control_bound": "add_control_bound"}
+
+
+def carried(o):
+    """the parameters of PARAMS the handle has an ingredient for (alg_kkt_sensitivity answers ALG_ERR_STATE for the others)"""
+    num = o._num
+    have = lambda q: (_pair_table(o, num) is not None) if q == "collision_radius" else INGREDIENT.get(q, "set_lqr") in num
+    return tuple(q for q in PARAMS if have(q))
+
+
 def numbers(o, g):
-    """the numbers of game g of batch o: Q, xf (p, ni), R, uf (p, mi), cc_r, cc_mu (p), pair (p, p) with a zero diagonal, umax, umin (m)"""
+    """the numbers of game g of batch o: Q, xf (p, ni), R, uf (p, mi), cc_r, cc_mu (p), pair (p, p) with a zero diagonal and its mask `on`
+    (p, p) of the ordered pairs that exist, umax, umin (m); an ingredient that was never added is absent"""
     num = o._num
     Q, R, xf, uf = num["set_lqr"]
     ni = o.n // o.p
     pick = lambda v, w: np.broadcast_to(v[g] if v.ndim == 3 else v, (o.p, w)).copy()
-    r = np.broadcast_to(num["add_collision_avoidance"][0], (o.p,))
-    pair = (r[:, None] + r[None, :]) * (1 - np.eye(o.p))
-    return dict(Q=pick(Q, ni), xf=pick(xf, ni), R=pick(R, o.mi), uf=pick(uf, o.mi), cc_r=num["add_collision_cost"][0].copy(),
-                cc_mu=num["add_collision_cost"][1].copy(), pair=pair, umax=num["add_control_bound"][0].copy(), umin=num["add_control_bound"][1].copy())
+    out = dict(Q=pick(Q, ni), xf=pick(xf, ni), R=pick(R, o.mi), uf=pick(uf, o.mi))
+    if "add_collision_cost" in num:
+        out.update(cc_r=num["add_collision_cost"][0].copy(), cc_mu=num["add_collision_cost"][1].copy())
+    tab = _pair_table(o, num)
+    if tab is not None:
+        out.update(pair=tab[0], on=tab[1])
+    if "add_control_bound" in num:
+        out.update(umax=num["add_control_bound"][0].copy(), umin=num["add_control_bound"][1].copy())
+    return out
 
 
 def param_len(o, param):
@@ -98,7 +146,8 @@ def analytic_rhs_game(o, g, param):
     """R = -d res / d theta of game g, (S, len), written down term by term from the oracle's residual (cost_grad_x / cost_grad_u and the
     collision-avoidance and control-bound blocks of `residual`, oracle/algames_oracle.cpp).  Also returns the activity of the rows the
     parameter enters: a list of 0 / 1 (collision_radius, control_bound: a = (c >= 0) | (lambda > 0) per finite row; collision_cost: the
-    pairs' r_i - |d| > 0): what the test counts active and inactive rows with."""
+    pairs' r_i - |d| > 0): what the test counts active and inactive rows with.  A parameter whose ingredient was never added is no parameter
+    of this handle (`carried`): zeros and no rows; a never-added pair of a partial pair table has no row and a zero column."""
     z, lam, mu = _game(o, g)
     num = numbers(o, g)
     n, m, p, mi, N, dt = o.n, o.m, o.p, o.mi, o.N, o.dt
@@ -106,6 +155,8 @@ def analytic_rhs_game(o, g, param):
     L = param_len(o, param)
     R = np.zeros((o.S, L))
     act = []
+    if param not in carried(o):
+        return R, act
     eps_n = EPS * np.sqrt(float(n))
     for k in range(N - 1):
         w = dt if k + 1 < N - 1 else 1.0
@@ -142,7 +193,7 @@ def analytic_rhs_game(o, g, param):
                             R[rx + a * p + j, col] -= w * dg
             elif param == "collision_radius":
                 for j in range(p):
-                    if j == i:
+                    if j == i or not num["on"][i, j]:
                         continue
                     Rr = num["pair"][i, j]
                     dims = getattr(o, "_dims", 2)                                                             # 3: the spherical form
@@ -179,16 +230,38 @@ def analytic_rhs(tw, param):
     return np.stack(out), act
 
 
-def _set(o, name, *args):
+def _set(o, name, *args, **kw):
     """Batch's own setter, past any wrapper that sits on the instance (kkt_reference.recording keeps the one it was given): o._num stays"""
     import algames_jl_amd as A
-    return getattr(A.Batch, name)(o, *args)
+    return getattr(A.Batch, name)(o, *args, **kw)
+
+
+def _set_pairs(o, pair, on):
+    """the collision avoidance of batch o rebuilt pair by pair from the table `pair` over the ordered pairs of `on`, in the batch's own form
+    (planar or spherical).  The spherical adders re-create the multipliers: they are put back."""
+    sph = getattr(o, "_dims", 2) == 3
+    lam, mu = o.get_con_duals()
+    o.lib.check((o.lib.add_spherical_collision_avoidance if sph else o.lib.add_collision_avoidance)(o.h, None))
+    for i in range(o.p):
+        for j in range(o.p):
+            if j != i and on[i, j]:
+                _set(o, PAIRS, i, j, pair[i, j], spherical=sph)
+    if sph:
+        assert o.get_con_duals()[0].shape == lam.shape
+        o.set_con_duals(lam, mu)
 
 
 def _apply(o, num):
     """the batch's numbers as recorded in `num` (the layout of o._num)"""
     for name in _SETTERS:
-        _set(o, name, *num[name])
+        if name in num and name != "add_collision_avoidance":
+            _set(o, name, *num[name])
+    tab = _pair_table(o, num)
+    if tab is not None:
+        if "add_collision_avoidance" in num and getattr(o, "_dims", 2) == 2:
+            _set(o, "add_collision_avoidance", *num["add_collision_avoidance"])
+        else:
+            _set_pairs(o, *tab)
 
 
 def _moved(o, param, c, s):
@@ -207,19 +280,20 @@ def _moved(o, param, c, s):
         num["add_control_bound"][c // m][c % m] += s
         _set(o, "add_control_bound", *num["add_control_bound"])
     else:
-        r = np.broadcast_to(num["add_collision_avoidance"][0], (p,))
-        pair = r[:, None] + r[None, :]
-        pair[c // p, c % p] += s
-        o.lib.check(o.lib.add_collision_avoidance(o.h, None))
-        for i in range(p):
-            for j in range(p):
-                if j != i:
-                    o.add_collision_avoidance_pair(i, j, pair[i, j])
+        pair, on = _pair_table(o, num)
+        pair = pair.copy()
+        pair[c // p, c % p] += s                                        # (the diagonal, a never-added pair: no parameter, nothing moves)
+        _set_pairs(o, pair, on)
+
+
+def _no_column(o, param, c):
+    """collision_radius: the diagonal of the pair table and a never-added pair are no parameters of the oracle"""
+    return param == "collision_radius" and not _pair_table(o, o._num)[1][c // o.p, c % o.p]
 
 
 def fd_rhs(tw, param, h):
     """R = -(res(theta + h e_c) - res(theta - h e_c)) / (2 h) per game, (B, S, len), of the oracle's residual; h: one step or one per column.
-    The diagonal of the pair table is no parameter of the oracle: its columns stay zero."""
+    The diagonal of the pair table and a never-added pair are no parameters of the oracle: their columns stay zero."""
     out, done = [None] * len(tw), {}
     for k, (o, g) in enumerate(tw):
         if id(o) not in done:
@@ -228,7 +302,7 @@ def fd_rhs(tw, param, h):
             saved = {k2: tuple(v.copy() for v in vs) for k2, vs in o._num.items()}
             R = np.zeros((o.B, o.S, L))
             for c in range(L):
-                if param == "collision_radius" and c // o.p == c % o.p:
+                if _no_column(o, param, c):
                     continue
                 rr = []
                 for s in (hs[c], -hs[c]):
@@ -305,7 +379,7 @@ def flips(tw, param, h):
     for o in {id(o): o for o, _ in tw}.values():
         hs = np.broadcast_to(np.asarray(h, dtype=np.float64), (param_len(o, param),))
         for c in range(len(hs)):
-            if param == "collision_radius" and c // o.p == c % o.p:
+            if _no_column(o, param, c):
                 continue
             act = []
             for s in (hs[c], -hs[c]):

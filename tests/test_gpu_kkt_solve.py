@@ -4,7 +4,8 @@ The reference is always the oracle's Jacobian with numpy's LAPACK solve (tests/k
 is held by tests/test_kkt_sensitivity_family.py on the CPU), never the HIP Jacobian.  One shape per kernel kind (kkt_reference.SHAPES: base
 tile path, unicycle, d = 1, EXT by a wall, bicycle, the block-reading twin with per-game pair radii, three dense kinds), horizons N in
 {2, 3, 5, 7, 9} and N - 1 = FT + 1 (dense kinds up to 7), four games.  Bounds: the direction test's -- status 0, |X - X_ref| <= 1e-9 max |X_ref|
-per column, |J X - R| <= 1e-8 max(1, |R|_inf)."""
+per column, |J X - R| <= 1e-8 max(1, |R|_inf).  The nine shapes are not the coverage of the kernel's configurations: all 79 run in
+tests/test_gpu_kkt_configs.py (the list: tests/kkt_config_family.py)."""
 import ctypes
 
 import numpy as np

@@ -5,7 +5,8 @@ The reference of a right-hand side is the one written down on the host (tests/pa
 oracle's residual by tests/test_param_reference.py on the CPU), evaluated at the oracle twin of the device's iterate; the reference of the
 solve is alg_kkt_solve(ALG_KKT_RHS_USER) on that right-hand side and the oracle's Jacobian -- never the HIP Jacobian.  Shapes, horizons and
 batch are test_gpu_kkt_solve's: the nine of kkt_reference.SHAPES over K.horizons(name), four games.  Bounds: status 0, |X - X_user| <= 1e-9
-max |X_user| per column, |J X - R| <= 1e-8 max(1, |R|_inf); a column whose right-hand side is zero is exactly zero."""
+max |X_user| per column, |J X - R| <= 1e-8 max(1, |R|_inf); a column whose right-hand side is zero is exactly zero.  The nine shapes are
+not the coverage of the kernel's configurations: all 79, per-game numbers and partial pair tables run in tests/test_gpu_kkt_configs.py."""
 import ctypes
 
 import numpy as np
