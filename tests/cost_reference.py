@@ -97,7 +97,16 @@ def closed_loop_cost(model, dt, hold, states, controls, Q, R, xf, uf, rad=None, 
 def bound(ref, w_mu_r2_pairs=None):
     """The tolerance of the device figures against this file, per component: 1e-12 (ref + w mu_i r_i^2 x pair terms), the second term on the
     collision component only.  Derived, not measured: all summands are non-negative, a total takes fewer than 5 000 rounding operations at
-    the tests' shapes (5 000 x 2^-53 = 5.6e-13), and the cancellation in r - |.| is absolute in r."""
+    the shapes of tests/test_gpu_cost.py (5 000 x 2^-53 = 5.6e-13), and the cancellation in r - |.| is absolute in r.
+
+    At the shapes of tests/test_gpu_log_configs.py the count of operations no longer serves (one quadrotor over 129 knots: about 6 200), and
+    it is not what bounds the error either: a sum of non-negative terms is off by at most (depth of the longest addition chain + the
+    roundings of one term) ulp, relative.  The chain of a device total: the terms of one item (at most the quadrotor's 12 state entries, or
+    p - 1 <= 9 pair terms), the factor 1/2 and the weight (2), the trips of a lane (ceil(knots / KPT) = 3 at knots = 2 KPT + 1), the lanes of
+    one player in cost_reduce (KPT <= 64); a term costs 3 roundings (difference, square, weight), a pair term a few more (two squares, a
+    square root, the gap).  One player, 129 knots (KPT = 64): 12 + 2 + 3 + 64 + 3 = 84 ulp = 9.3e-15.  Two quadrotors, 65 knots (KPT = 32):
+    12 + 2 + 3 + 32 + 3 = 52 ulp = 5.8e-15.  This file adds the same terms knot after knot: a chain of at most 130 knots + 15 = 1.6e-14.
+    Device and reference together stay below 2.6e-14, a fortieth of the 1e-12: the constant stands."""
     tol = 1e-12 * np.abs(ref)
     if w_mu_r2_pairs is not None:
         tol[..., 2] = tol[..., 2] + 1e-12 * w_mu_r2_pairs
